@@ -18,9 +18,24 @@ are comparable.  Elements shard embarrassingly: every rank owns a contiguous sla
 the global element range and there is no data-path collective (weak scaling).
 
 Rank 0 prints ONE JSON line: metric/value (whole-job element updates per second),
-"roofline" for the dominant kernel (algorithmic bytes per launch / HIP-event
-kernel time, against the 8 TB/s HBM3E peak) and "cpu_baseline" (the reference's
-own serial C++ path, or this repo's C port of it, on the host cores; N=1 only).
+ms_per_step and "roofline" for the dominant kernel (algorithmic bytes per launch /
+HIP-event kernel time of the timed steps, against the 8 TB/s HBM3E peak).  A plain
+run does only that: set up, spin up and warm up, time the K steps, print the line.
+
+--full adds everything else this script measures, outside the timed region: the
+all-streaming twin, per-launch spread, the kernel's own traffic skeleton, the other
+BASELINE configurations (fresh child processes), live HBM counters, the driver loop
+as one launch, host sequences, placement spread, measured ceilings, the drop-in
+driver and "cpu_baseline" (the reference's own serial C++ path, or this repo's C
+port of it, on the host cores; N=1 only).  The --no-* options skip parts of it.
+
+--dump-outputs DIR writes, right after the timed steps, what the last timed step
+computed: every array compute_and_apply_rhs writes (the state at np1 and the derived
+fields), as float64 DIR/<array name>.npy for a fixed, seeded sample of rank 0's
+elements (DIR/element_index.npy holds their global indices), at most 48 MiB in all.
+The arrays it writes are restored to their initial values before the W warmup
+steps, so the inputs of the last step depend on the arguments only (the derived
+fields accumulate over the W + K steps) and two builds can be compared file for file.
 """
 import argparse
 import json
@@ -50,6 +65,12 @@ def parse():
     ap.add_argument("--total-elems", type=int, default=None,
                     help="total elements of the job, cut into contiguous slabs of ceil(E/N) (overrides "
                          "--elems-per-gpu; the last rank may hold fewer)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline (see the module docstring); the --no-* options "
+                         "below skip parts of it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<array name>.npy (float64, a "
+                         "seeded sample of rank 0's elements, <= 48 MiB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--isolated", action="store_true", help="(default since round 4; accepted for old command lines)")
     ap.add_argument("--no-isolated", action="store_true",
@@ -219,12 +240,12 @@ def cpu_baseline(np_, nlev, seconds, elems=10000):
 
 def measure_config(np_, nlev, elems, steps, warmup):
     """One more configuration, measured by this same script in a FRESH process (the headline line of a child run with
-    --no-other-configs): where the driver places the arrays moves the rate by 3-5 % (DESIGN.md section 5 "Placement"), and
+    --full --no-other-configs): where the driver places the arrays moves the rate by 3-5 % (DESIGN.md section 5 "Placement"), and
     arrays allocated after the allocate/free traffic of a long-running process tend to land badly; a fresh process is what
     a host running that configuration would be."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--np", str(np_), "--nlev", str(nlev),
-           "--elems-per-gpu", str(elems), "--steps", str(steps), "--warmup", str(warmup), "--no-other-configs",
+           "--elems-per-gpu", str(elems), "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-other-configs",
            "--no-cpu-baseline", "--no-interleaved", "--no-live-traffic", "--no-dropin"]
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
@@ -750,6 +771,32 @@ def dropin_leg(np_, nlev, elems, kernel_ms, timeout=300):
     return out
 
 
+# the arrays compute_and_apply_rhs writes: the state at time level np1 and the derived fields (the last three accumulate)
+OUTPUT_NAMES = ("elem_state_dp3d", "elem_state_v", "elem_state_T", "elem_derived_phi",
+                "elem_derived_eta_dot_dpdn", "elem_derived_omega_p", "elem_derived_vn0")
+DUMP_BUDGET_BYTES = 48 << 20
+DUMP_SEED = 20240611
+
+
+def dump_outputs(torch, data, out_dir, first_elem, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what the last step wrote, as float64 out_dir/<name>.npy (state arrays: time level np1 only) for a
+    seeded sample of this rank's elements that fits `budget` (all of them when they fit), plus element_index.npy (global
+    element indices of the sample, float64).  Returns a short description for the JSON line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np1, ne = data.control.np1, data.arrays.num_elems
+    views = {n: (data.arrays[n][:, np1] if n.startswith("elem_state_") else data.arrays[n]) for n in OUTPUT_NAMES}
+    per_elem = sum(v[0].numel() * 8 for v in views.values())
+    n = max(1, min(ne, budget // per_elem))
+    idx = np.arange(ne) if n == ne else np.sort(np.random.RandomState(DUMP_SEED).choice(ne, n, replace=False))
+    it = torch.as_tensor(idx, dtype=torch.long, device=views[OUTPUT_NAMES[0]].device)
+    for name, v in views.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v.index_select(0, it).cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "element_index.npy"), (idx + first_elem).astype(np.float64))
+    return {"dir": out_dir, "elements": int(n), "of_elements": int(ne), "time_level": int(np1),
+            "arrays": list(OUTPUT_NAMES) + ["element_index"], "bytes": int(n * per_elem + n * 8)}
+
+
 def self_launch(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: this process starts the N ranks itself and only
     waits for them.  It imports neither torch nor the library, so nothing here has initialised the GPU (no exec of an
@@ -854,6 +901,8 @@ def main():
     mine = nete - nets
     data = tsa.TestData().init_data(mine, args.np_, args.nlev, device=dev, first_elem=nets)
     stream = torch.cuda.current_stream(dev)
+    # --dump-outputs: the initial values of the arrays the step writes, put back before the warmup steps (see below)
+    initial = {n: data.arrays[n].clone() for n in OUTPUT_NAMES} if args.dump_outputs else None
 
     def barrier():
         if dist is not None:
@@ -863,6 +912,13 @@ def main():
     tsa.compute_and_apply_rhs(data, stream)
     torch.cuda.synchronize(dev)
     spin = [] if args.no_spinup else spin_up(tsa, torch, data, stream, dev)
+    if initial is not None:
+        # the spin-up makes a timing-dependent number of calls and the derived fields accumulate: from here on exactly
+        # W + K calls, so the dumped outputs depend on the arguments only
+        for n, t in initial.items():
+            data.arrays[n].copy_(t)
+        del initial   # (kept in torch's cache: memory handed back to the driver now could stall the timed launches)
+        torch.cuda.synchronize(dev)
 
     for _ in range(args.warmup):
         tsa.compute_and_apply_rhs(data, stream)
@@ -890,13 +946,15 @@ def main():
     wall_max, kernel_ms_max, wall_with_barrier_max = sharding.max_over_ranks([wall, kernel_ms, wall_with_barrier], dist,
                                                                              reduce_dev)
     per_rank = sharding.gather_over_ranks([float(mine), kernel_ms], dist, reduce_dev)  # [[elems, ms], ...]
+    # what the last timed step computed, before anything else runs on the arrays
+    dumped = dump_outputs(torch, data, args.dump_outputs, nets) if args.dump_outputs and rank == 0 else None
 
     # The default NP=4 kernels keep the read-modify-write accumulators of part of the elements in the
     # Infinity Cache between calls (caar_set_cache_window): bench.py replays the same arrays back to back,
     # so those bytes are served on-chip and `achieved` above is ALGORITHMIC throughput, not DRAM
-    # throughput.  The same launches with every access streaming (window 0), outside the timed region:
+    # throughput.  The same launches with every access streaming (window 0), outside the timed region (--full):
     kernel_ms_streaming = None
-    if args.np_ == 4 and lib.caar_num_variants(args.np_, args.nlev) > 1:
+    if args.full and args.np_ == 4 and lib.caar_num_variants(args.np_, args.nlev) > 1:
         # variant 1 of every NP=4 table is the all-streaming (non-temporal, no cache window) form of variant 0:
         # same launch shape, another kernel name, so a rocprofv3 --stats run of this command keeps the two apart
         lib.caar_select_variant(args.np_, args.nlev, 1)
@@ -910,10 +968,11 @@ def main():
     #    the conditions of the timed region (its predecessor's write-back still draining) -> kernel_ms_median / kernel_ms_min;
     #  * isolated: one event pair per launch, the stream idle before each (~4 % shorter: a launch that starts on an idle
     #    chip does not share HBM with its predecessor's dirty lines) -> kernel_ms_isolated_*.
-    # `value` and roofline.achieved use the mean of the timed region above.  --no-isolated skips both (a rocprofv3 --stats
-    # run then sees only spin-up, warm-up and timed launches of this grid; tools/trace_stats.py --window cuts either way).
+    # `value` and roofline.achieved use the mean of the timed region above.  Only with --full; --no-isolated skips both (a
+    # rocprofv3 --stats run then sees only spin-up, warm-up and timed launches of this grid; tools/trace_stats.py --window
+    # cuts either way).
     per_launch, back_to_back = [], []
-    if rank == 0 and not args.no_isolated:
+    if rank == 0 and args.full and not args.no_isolated:
         n = max(args.steps, 20)
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(n + 1)]
         tsa.compute_and_apply_rhs(data, stream)
@@ -932,6 +991,7 @@ def main():
         per_launch = sorted(a.elapsed_time(b) for a, b in pairs)
 
     if rank == 0:
+        extras = world == 1 and args.full   # the single-GPU measurements beyond the headline
         balg = tsa.algorithmic_bytes(args.np_, args.nlev)
         per_launch_bytes = balg * mine
         achieved = per_launch_bytes / (kernel_ms_max * 1e-3) / 1e9
@@ -998,7 +1058,7 @@ def main():
                                 "achieved": balg * e / (ms * 1e-3) / 1e9,
                                 "frac": balg * e / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
                                for r, (e, ms) in enumerate(per_rank)]
-        if world == 1:
+        if extras:
             # the kernel against ITS OWN traffic with the arithmetic taken out, on the same arrays, same cache policy and window,
             # replayed like the kernel (outside the timed region; the skeleton's stores only touch what the next call overwrites)
             sk = own_traffic_skeleton(tsa, torch, data, dev, args.np_, args.nlev, mine)
@@ -1041,6 +1101,8 @@ def main():
             "hbm_gbs_algorithmic_job": total_elems * args.steps * balg / wall_max / 1e9,
             "roofline": roof,
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if world > 1:
             # the N=1 line holds another per-GPU size (10 000 = configs[1]); the N=1 figure that is comparable with this
             # line — same kernel, same elements per GPU — is measured by the N=1 run in a child process:
@@ -1050,7 +1112,7 @@ def main():
                 "why": "--gpus 1 is BASELINE configs[1] (10 000 elements); --gpus N>1 holds %d per GPU so that --gpus 8 is "
                        "configs[2]; efficiency against the headline N=1 value mixes in the size effect" % mine,
             }
-        if world == 1 and not args.no_other_configs and (args.np_, args.nlev) == (4, 72):
+        if extras and not args.no_other_configs and (args.np_, args.nlev) == (4, 72):
             # kernel-only, same run; the headline stays configs[1]:
             #  * 12 500 elements NP=4 NLEV=72 = one GPU's share of configs[2] (what --gpus 8 runs per GPU)
             #  * configs[3] NP=4 NLEV=128, one GPU's share of 100 000 elements
@@ -1058,7 +1120,7 @@ def main():
             # (the headline arrays stay allocated: freeing and re-allocating them would change what placement_spread sees)
             out["other_configs"] = [measure_config(4, 72, 12500, 20, 5), measure_config(4, 128, 12500, 20, 5),
                                     measure_config(8, 72, 20000, 10, 3)]
-        if world == 1 and not args.no_live_traffic:
+        if extras and not args.no_live_traffic:
             # the arrays of this process stay allocated: the children hold their own (2-4 GB) for a few seconds
             lt = live_traffic(args.np_, args.nlev, mine)
             if lt is not None:
@@ -1066,7 +1128,7 @@ def main():
                 roof["traffic_source"] = TRAFFIC_SOURCE_LIVE
                 roof["traffic_detail"] = lt
                 roof["traffic_over_algorithmic"] = lt["bytes"] / per_launch_bytes
-        if world == 1 and not args.no_steps_leg:
+        if extras and not args.no_steps_leg:
             # caar_run_steps / caar_launch_steps: not part of `value`
             roof["run_steps"] = rs = run_steps_leg(tsa, torch, args, data, dev, stream, mine)
             st = (roof.get("traffic_detail") or {}).get("steps")
@@ -1078,7 +1140,7 @@ def main():
                                        "hbm_bytes_over_single_call_algorithmic": per_call / per_launch_bytes,
                                        "hbm_kernel": st["kernel"], "hbm_source": TRAFFIC_SOURCE_LIVE,
                                        "issue": issue_profile(st["kernel"])})
-        if world == 1 and not args.no_interleaved:
+        if extras and not args.no_interleaved:
             seqs = interleaved_sequences(tsa, torch, args, data, dev, stream, mine, args.steps)
             roof["interleaved"] = seqs
             # CAAR inside the reference's driver loop with rotation and a tracer step between the calls ...
@@ -1087,10 +1149,10 @@ def main():
             # ... and with a neighbour that wipes the Infinity Cache between the calls
             roof["achieved_interleaved_evicting"] = seqs["evicting"]["default"]["achieved"]
             roof["frac_interleaved_evicting"] = seqs["evicting"]["default"]["frac"]
-        if world == 1 and not args.no_interleaved and args.np_ == 4:
+        if extras and not args.no_interleaved and args.np_ == 4:
             # four host threads / streams on disjoint quarters of the arrays (the reference's horizontal-OpenMP pattern)
             roof["subrange_streams"] = subrange_streams_leg(tsa, torch, args, data, dev, stream, mine, steps=args.steps)
-        if world == 1 and not args.no_other_configs:
+        if extras and not args.no_other_configs:
             # the same step on [the timed allocation, two more placed allocations, plain torch allocations] (GB/s)
             roof["placement_spread_achieved"] = placement_spread(tsa, torch, args, data, dev, stream, mine, nets)
             del data
@@ -1104,9 +1166,9 @@ def main():
             # (measured_on_this_box.traffic_skeleton_hybrid_GBs is the hybrid skeleton on a FRESH allocation made at the end of
             # this process: placement differs from the timed arrays' by up to 5 %; the like-for-like ratio is
             # roofline.frac_of_own_traffic_skeleton, measured on the timed arrays themselves)
-        if world == 1 and not args.no_dropin and not args.no_other_configs:
+        if extras and not args.no_dropin and not args.no_other_configs:
             out["dropin"] = dropin_leg(args.np_, args.nlev, mine, kernel_ms_max)
-        if world == 1 and not args.no_cpu_baseline:
+        if extras and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.np_, args.nlev, args.cpu_seconds, mine)
         print(json.dumps(out))
     if dist is not None:

@@ -4,6 +4,8 @@ integer-hash pseudo-random numbers (splitmix64 on uint64: exactly reproducible o
 every platform) or from the reference's closed-form initialiser; only the
 reference's OUTPUTS live in tests/golden/*.npz.
 """
+import hashlib
+import json
 import os
 import sys
 
@@ -149,3 +151,83 @@ def scaled_err(got, want):
     accumulated diagnostics whose individual entries can cancel to ~0)."""
     m = float(np.max(np.abs(want)))
     return float(np.max(np.abs(got - want))) / (m if m > 0 else 1.0)
+
+
+# ---- the live-reference checks of tests/test_oracle.py.  Their inputs are built here, and reference_results() computes
+#      what the reference returns for them through oracle/_ref (where it is built); tests/golden/make_golden.py --digests
+#      records the digests of those results in REFERENCE_DIGESTS, so that the checks also run where oracle/_ref is not.
+REFERENCE_DIGESTS = os.path.join(GOLDEN_DIR, "reference_digests.json")
+OPERATOR_NPS = (4, 8)
+ALIASED_LEVELS = ((0, 1, 0), (1, 1, 0), (0, 1, 1), (2, 2, 2))
+INIT_SCALARS = ("n0", "np1", "nm1", "qn0", "dt2", "rrearth", "eta_ave_w", "Rwater_vapor", "Rgas", "kappa", "ps0")
+
+
+def digest(a):
+    """SHA-256 of an array's float64 values in C order, -0.0 read as 0.0: two arrays have the same digest exactly when
+    np.array_equal holds for them (finite values)."""
+    return hashlib.sha256((np.ascontiguousarray(a, dtype=np.float64) + 0.0).tobytes()).hexdigest()
+
+
+def reference_digests():
+    with open(REFERENCE_DIGESTS) as f:
+        return json.load(f)
+
+
+def operator_case(np_):
+    """-> (arrays, Dvv, rrearth, [(element, scalar field, vector field), ...])"""
+    arrs = hashed_arrays(np_, 72, 2, seed=11)
+    fields = [(ie, uniform((np_, np_), 77 + ie, -3, 5), uniform((np_, np_, 2), 99 + ie, -3, 5)) for ie in range(2)]
+    return arrs, dvv_for(np_, "double" if np_ == 4 else "gll"), 0.37, fields
+
+
+def aliased_case(levels):
+    """Coinciding time-level indices (n0, np1, nm1) = levels -> (arrays, Dvv, scalars)"""
+    arrs = hashed_arrays(4, 72, 2, seed=140)
+    sc = po.default_scalars(72)
+    sc.update(n0=levels[0], np1=levels[1], nm1=levels[2], qn0=1, dt2=0.25, eta_ave_w=0.5)
+    return arrs, dvv_for(4), sc
+
+
+def aliased_key(levels):
+    return "aliased_%d%d%d" % tuple(levels)
+
+
+def reference_operators(R, np_):
+    """gradient / divergence / vorticity of operator_case(np_) by the reference (R: po.Reference(np_, 72))"""
+    arrs, Dvv, rr, fields = operator_case(np_)
+    out = {}
+    for ie, s, v in fields:
+        k = "operators_np%d/%d/" % (np_, ie)
+        out[k + "gradient"] = R.sphere_operator(0, s, arrs, ie, rr, Dvv)
+        out[k + "divergence"] = R.sphere_operator(1, v, arrs, ie, rr, Dvv)
+        out[k + "vorticity"] = R.sphere_operator(2, v, arrs, ie, rr, Dvv)
+    return out
+
+
+def reference_init(R, ne=5):
+    """The reference's TestData::init_data for `ne` elements and its compute_norm of one field (R: po.Reference(4, 72))"""
+    arrs, Dvv, sc = R.init_data(ne)
+    out = {"init/" + n: arrs[n] for n in po.ARRAY_NAMES}
+    out.update({"init/Dvv": Dvv, "init/hyai": sc["hyai"], "init/scalars": np.array([sc[k] for k in INIT_SCALARS], dtype=float),
+                "init/norm": np.array([R.compute_norm(arrs["elem_state_v"][0, 1])])})
+    return out
+
+
+def reference_aliased(R, levels):
+    """Every array after one reference call on aliased_case(levels) (R: po.Reference(4, 72))"""
+    arrs, Dvv, sc = aliased_case(levels)
+    b = copy_arrays(arrs)
+    R.compute_and_apply_rhs(b, Dvv, sc)
+    return {aliased_key(levels) + "/" + n: b[n] for n in po.ARRAY_NAMES}
+
+
+def reference_results():
+    """Everything the live-reference checks compare with, computed by oracle/_ref."""
+    out = {}
+    for np_ in OPERATOR_NPS:
+        out.update(reference_operators(po.Reference(np_, 72), np_))
+    R = po.Reference(4, 72)
+    out.update(reference_init(R))
+    for levels in ALIASED_LEVELS:
+        out.update(reference_aliased(R, levels))
+    return out

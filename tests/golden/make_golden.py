@@ -20,7 +20,10 @@ Produces
                                   compute_and_apply_rhs_test/fortran/test_mod.F90:8-882
   fortran_orig_stdout.txt         stdout of the reference's unmodified Fortran driver
                                   (oracle/_ref/fortran_orig: golden self-check + norms)
+  reference_digests.json          (--digests, alone) SHA-256 digests of the reference's results
+                                  for the live-reference checks of tests/test_oracle.py
 """
+import json
 import os
 import re
 import subprocess
@@ -103,5 +106,19 @@ def main():
     print("wrote fortran_test_mod_vectors.npz, fortran_orig_stdout.txt")
 
 
+def write_digests():
+    """reference_digests.json only: the digests of what the reference returns for the live-reference checks of
+    tests/test_oracle.py (cases.reference_results)."""
+    po.build(ref=True)
+    res = cases.reference_results()
+    with open(cases.REFERENCE_DIGESTS, "w") as f:
+        json.dump({k: cases.digest(v) for k, v in sorted(res.items())}, f, indent=1)
+        f.write("\n")
+    print("wrote", os.path.basename(cases.REFERENCE_DIGESTS), len(res), "digests")
+
+
 if __name__ == "__main__":
-    main()
+    if "--digests" in sys.argv[1:]:
+        write_digests()
+    else:
+        main()

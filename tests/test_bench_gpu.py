@@ -28,9 +28,9 @@ def _clean_env():
 
 
 def test_single_gpu_line_carries_the_contract_and_the_host_sequences():
-    r = subprocess.run([sys.executable, BENCH, "--elems-per-gpu", "1500", "--steps", "4", "--warmup", "2", "--no-spinup",
-                        "--no-other-configs", "--cpu-seconds", "0.2"], capture_output=True, text=True, timeout=900,
-                       env=_clean_env())
+    r = subprocess.run([sys.executable, BENCH, "--full", "--elems-per-gpu", "1500", "--steps", "4", "--warmup", "2",
+                        "--no-spinup", "--no-other-configs", "--cpu-seconds", "0.2"], capture_output=True, text=True,
+                       timeout=900, env=_clean_env())
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     j = _line(r.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -101,6 +101,48 @@ def test_single_gpu_line_carries_the_contract_and_the_host_sequences():
     assert cb["cpu_model"] and cb["nproc"] >= cb["cores"] and "-O3" in cb["flags"] or cb["kind"] == "port"
     one = cb["single_core"]
     assert one["elements"] == 1500 and one["calls"] >= 3 and len(one["seconds_per_call"]) == one["calls"] and one["value"] > 0
+
+
+def test_plain_line_is_the_headline_and_dumped_outputs_match_the_oracle(tmp_path, oracle):
+    """Without --full the run is the headline alone: set-up, spin-up, W warmup and K timed steps, the line.
+    --dump-outputs writes what the last timed step computed; with the written arrays put back before the warmup, the
+    dump is the state after exactly W + K calls on the closed-form arrays: the same in two processes, and the oracle's."""
+    import numpy as np
+    import cases
+    from oracle import pyoracle as po
+    ne, steps, warmup = 1500, 4, 2
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                            "--elems-per-gpu", str(ne), "--dump-outputs", str(d)], capture_output=True, text=True,
+                           timeout=600, env=_clean_env())
+        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+        j = _line(r.stdout)
+        assert j["steps"] == steps and j["warmup"] == warmup and j["ms_per_step"] > 0 and j["dtype"] == "f64"
+        assert abs(j["value"] - ne / (j["ms_per_step"] * 1e-3)) <= 1e-6 * j["value"]
+        for k in ("cpu_baseline", "other_configs", "dropin"):
+            assert k not in j, k
+        for k in ("achieved_all_streaming", "interleaved", "subrange_streams", "run_steps", "measured_on_this_box",
+                  "traffic_skeleton_own_policy_GBs"):
+            assert k not in j["roofline"], k
+        assert j["roofline"]["kernel_ms_median"] is None and j["roofline"]["achieved"] > 0
+        files = sorted(os.listdir(d))
+        assert files == sorted(n + ".npy" for n in j["dump_outputs"]["arrays"]), files
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        dumps.append({f[:-4]: np.load(d / f) for f in files})
+    a, b = dumps
+    for n in a:
+        assert a[n].dtype == np.float64 and np.array_equal(a[n], b[n]), n
+    idx = a["element_index"].astype(np.int64)   # 1500 elements (124 MB of outputs) are sampled
+    assert 0 < len(idx) < ne and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < ne
+    assert all(a[n].shape[0] == len(idx) for n in a)
+    arrs = oracle.init_arrays(4, 72, 1, 3, ne)
+    sc = po.default_scalars(72)
+    oracle.compute_and_apply_rhs(arrs, oracle.dvv_np4(False), sc, reps=warmup + steps)
+    for n in cases.OUTPUT_NAMES:
+        want = arrs[n][idx, sc["np1"]] if n.startswith("elem_state_") else arrs[n][idx]
+        assert cases.scaled_err(a[n], want) <= 1e-12, (n, cases.scaled_err(a[n], want))
 
 
 @pytest.mark.parametrize("launcher", ["plain", "torch.distributed.run"])

@@ -5,8 +5,9 @@
  2. committed outputs of the reference C++ path (cxx/pointers_only) and Fortran routine
     (fortran/routine_mod.F90) for every case in tests/cases.py (tests/golden/*.npz,
     produced by tests/golden/make_golden.py from oracle/_ref),
- 3. when oracle/_ref is present (build container), the live reference library,
-    operator by operator.
+ 3. the reference library operator by operator, on its initialiser and with aliased time
+    levels: live where oracle/_ref is built, else through the digests of its results
+    (tests/golden/reference_digests.json, produced by tests/golden/make_golden.py --digests).
 """
 import os
 
@@ -151,61 +152,55 @@ def test_derivative_matrix_pinned_without_its_generator(oracle, np_, which):
         assert np.max(np.abs(R - D)) < 2e-15
 
 
-needs_ref = pytest.mark.skipif(not po.have_reference(4, 72),
-                               reason="oracle/_ref not built (needs /root/reference)")
+LIVE_REFERENCE = all(po.have_reference(np_, 72) for np_ in cases.OPERATOR_NPS)
 
 
-@needs_ref
+def check_against_reference(got, live):
+    """got: the oracle's results by key.  Where oracle/_ref is built, the reference computes the same keys now (live())
+    and every array must equal it; everywhere, every array must have the digest recorded from the reference's result
+    (tests/golden/reference_digests.json, tests/golden/make_golden.py --digests)."""
+    if LIVE_REFERENCE:
+        want = live()
+        for k, a in got.items():
+            assert np.array_equal(a, want[k]), k
+    recorded = cases.reference_digests()
+    for k, a in got.items():
+        assert cases.digest(a) == recorded[k], k
+
+
 @pytest.mark.parametrize("np_,nlev", [(4, 72), (8, 72)])
 def test_live_reference_operators(oracle, np_, nlev):
-    R = po.Reference(np_, nlev)
-    arrs = cases.hashed_arrays(np_, nlev, 2, seed=11)
-    Dvv = cases.dvv_for(np_, "double" if np_ == 4 else "gll")
-    rr = 0.37
-    for ie in range(2):
-        s = cases.uniform((np_, np_), 77 + ie, -3, 5)
-        v = cases.uniform((np_, np_, 2), 99 + ie, -3, 5)
-        g = oracle.gradient_sphere(s, Dvv, arrs["elem_Dinv"][ie], rr)
-        d = oracle.divergence_sphere(v, Dvv, arrs["elem_Dinv"][ie], arrs["elem_metdet"][ie],
-                                     arrs["elem_rmetdet"][ie], rr)
-        w = oracle.vorticity_sphere(v, Dvv, arrs["elem_D"][ie], arrs["elem_rmetdet"][ie], rr)
-        assert np.array_equal(g, R.sphere_operator(0, s, arrs, ie, rr, Dvv))
-        assert np.array_equal(d, R.sphere_operator(1, v, arrs, ie, rr, Dvv))
-        assert np.array_equal(w, R.sphere_operator(2, v, arrs, ie, rr, Dvv))
+    arrs, Dvv, rr, fields = cases.operator_case(np_)
+    got = {}
+    for ie, s, v in fields:
+        k = "operators_np%d/%d/" % (np_, ie)
+        got[k + "gradient"] = oracle.gradient_sphere(s, Dvv, arrs["elem_Dinv"][ie], rr)
+        got[k + "divergence"] = oracle.divergence_sphere(v, Dvv, arrs["elem_Dinv"][ie], arrs["elem_metdet"][ie],
+                                                         arrs["elem_rmetdet"][ie], rr)
+        got[k + "vorticity"] = oracle.vorticity_sphere(v, Dvv, arrs["elem_D"][ie], arrs["elem_rmetdet"][ie], rr)
+    check_against_reference(got, lambda: cases.reference_operators(po.Reference(np_, nlev), np_))
 
 
-@needs_ref
 def test_live_reference_init_and_norm(oracle):
-    R = po.Reference(4, 72)
-    arrs_r, Dvv_r, sc_r = R.init_data(5)
     arrs_o = oracle.init_arrays(4, 72, 1, 3, 5)
-    for n in po.ARRAY_NAMES:
-        assert np.array_equal(arrs_r[n], arrs_o[n]), n
-    assert np.array_equal(Dvv_r, oracle.dvv_np4(False))
     sc = po.default_scalars(72)
-    for k in ("n0", "np1", "nm1", "qn0", "dt2", "rrearth", "eta_ave_w", "Rwater_vapor", "Rgas", "kappa", "ps0"):
-        assert sc[k] == sc_r[k], k
-    assert np.array_equal(sc["hyai"], sc_r["hyai"])
-    f = arrs_o["elem_state_v"][0, 1]
-    assert oracle.compute_norm(f) == R.compute_norm(f)
+    got = {"init/" + n: arrs_o[n] for n in po.ARRAY_NAMES}
+    got.update({"init/Dvv": oracle.dvv_np4(False), "init/hyai": sc["hyai"],
+                "init/scalars": np.array([sc[k] for k in cases.INIT_SCALARS], dtype=float),
+                "init/norm": np.array([oracle.compute_norm(arrs_o["elem_state_v"][0, 1])])})
+    check_against_reference(got, lambda: cases.reference_init(po.Reference(4, 72), 5))
 
 
-@needs_ref
-@pytest.mark.parametrize("levels", [(0, 1, 0), (1, 1, 0), (0, 1, 1), (2, 2, 2)])
+@pytest.mark.parametrize("levels", list(cases.ALIASED_LEVELS))
 def test_live_reference_aliased_time_levels(oracle, levels):
     """Coinciding time-level indices (HOMME's Runge-Kutta stages): the oracle follows the
     reference's statement order (all n0 reads before the update loop, P:236-257), so it
     has to stay bit-identical when n0, np1 and nm1 alias."""
-    R = po.Reference(4, 72)
-    arrs = cases.hashed_arrays(4, 72, 2, seed=140)
-    Dvv = cases.dvv_for(4)
-    sc = po.default_scalars(72)
-    sc.update(n0=levels[0], np1=levels[1], nm1=levels[2], qn0=1, dt2=0.25, eta_ave_w=0.5)
-    a, b = cases.copy_arrays(arrs), cases.copy_arrays(arrs)
+    arrs, Dvv, sc = cases.aliased_case(levels)
+    a = cases.copy_arrays(arrs)
     oracle.compute_and_apply_rhs(a, Dvv, sc)
-    R.compute_and_apply_rhs(b, Dvv, sc)
-    for n in po.ARRAY_NAMES:
-        assert np.array_equal(a[n], b[n]), n
+    got = {cases.aliased_key(levels) + "/" + n: a[n] for n in po.ARRAY_NAMES}
+    check_against_reference(got, lambda: cases.reference_aliased(po.Reference(4, 72), levels))
 
 
 def eulerian_case(np_=4, nlev=72, ne=2, seed=150):

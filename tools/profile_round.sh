@@ -1,6 +1,6 @@
 #!/bin/bash
 # Profiles of one round, run on the MI355X box:  bash tools/profile_round.sh r02
-#   1. rocprofv3 --kernel-trace --stats of the default bench.py command (per-kernel average durations)
+#   1. rocprofv3 --kernel-trace --stats of bench.py --full (per-kernel average durations)
 #   2. rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, of tools/pmc_run.py for every BASELINE config
 #      (HBM-side bytes per launch, calibrated on the stream copies of the same run; tools/pmc_parse.py)
 # Results land under gpurun_out/<round>/prof/; copy what is to be judged into profiles/<round>/.
@@ -13,9 +13,9 @@ export TMPDIR=/tmp
 cd /tmp
 PARTS=${2:-trace,pmc}
 if [[ $PARTS == *trace* ]]; then
-echo "[profile] bench.py under rocprofv3 --kernel-trace --stats"
+echo "[profile] bench.py --full under rocprofv3 --kernel-trace --stats"
 rm -rf "$OUT/bench_trace"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_trace" -- python3 "$ROOT/bench.py" > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_trace" -- python3 "$ROOT/bench.py" --full > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err"
 cp "$(find "$OUT/bench_trace" -name '*kernel_stats.csv' | head -1)" "$OUT/bench_kernel_stats.csv"
 python3 "$ROOT/tools/trace_stats.py" "$OUT/bench_trace" "--window=$OUT/bench_under_rocprof.json" > "$OUT/bench_kernel_stats_by_grid.csv"
 tail -1 "$OUT/bench_kernel_stats_by_grid.csv" | cut -c1-260
