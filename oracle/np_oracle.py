@@ -133,28 +133,63 @@ def compute_and_apply_rhs(arrs, Dvv, sc, dtype=np.float64):
 # repository's index convention (field[a][b] == Fortran (a+1, b+1), tensors [a][b][r][c] == Fortran
 # (., ., r+1, c+1), Dvv[i][j] == Fortran Dvv(i+1, j+1)) with einsum contractions — NOT through the accessor
 # macros of sphere_ops_oracle.c, so an index slip there does not repeat here.  Test infrastructure only.
+#
+# Batched: fields are [..., np, np](, 2) and the geometry [..., np, np](...) broadcasts against their leading axes
+# (one element: no leading axes; [ne][nlev] fields: geometry [ne][1][np][np]..., see ops_apply).  Any float dtype:
+# numpy.longdouble inputs give the 80-bit evaluation.  rmetdet: multiply by the stored reciprocal instead of dividing
+# by metdet (what the HIP kernels do), so that the longdouble result is the exact operator on the kernels' inputs.
+def _da(Dvv, f):  # sum_k Dvv[k][a] f[k][b]
+    return np.einsum("ka,...kb->...ab", Dvv, f)
+
+
+def _db(Dvv, f):  # sum_k Dvv[k][b] f[a][k]
+    return np.einsum("kb,...ak->...ab", Dvv, f)
+
+
+def _wa(Dvv, f):  # sum_k Dvv[a][k] f[k][b]
+    return np.einsum("ak,...kb->...ab", Dvv, f)
+
+
+def _wb(Dvv, f):  # sum_k Dvv[b][k] f[a][k]
+    return np.einsum("bk,...ak->...ab", Dvv, f)
+
+
+def _over_metdet(x, metdet, rmetdet):
+    return x / metdet if rmetdet is None else x * rmetdet
+
+
 def ops_gradient_sphere(s, Dvv, Dinv, rr):
-    v1 = np.einsum("il,ij->lj", Dvv, s) * rr
-    v2 = np.einsum("il,ji->jl", Dvv, s) * rr
+    v1 = _da(Dvv, s) * rr
+    v2 = _db(Dvv, s) * rr
     return np.stack([Dinv[..., 0, 0] * v1 + Dinv[..., 1, 0] * v2, Dinv[..., 0, 1] * v1 + Dinv[..., 1, 1] * v2], axis=-1)
 
 
-def ops_divergence_sphere(v, Dvv, Dinv, metdet, rr):
+def ops_divergence_sphere(v, Dvv, Dinv, metdet, rr, rmetdet=None):
     gv0 = metdet * (Dinv[..., 0, 0] * v[..., 0] + Dinv[..., 0, 1] * v[..., 1])
     gv1 = metdet * (Dinv[..., 1, 0] * v[..., 0] + Dinv[..., 1, 1] * v[..., 1])
-    return (np.einsum("il,ij->lj", Dvv, gv0) + np.einsum("il,ji->jl", Dvv, gv1)) / metdet * rr
+    return _over_metdet(_da(Dvv, gv0) + _db(Dvv, gv1), metdet, rmetdet) * rr
 
 
-def ops_vorticity_sphere(v, Dvv, D, metdet, rr):
+def ops_vorticity_sphere(v, Dvv, D, metdet, rr, rmetdet=None):
     vc0 = D[..., 0, 0] * v[..., 0] + D[..., 1, 0] * v[..., 1]
     vc1 = D[..., 0, 1] * v[..., 0] + D[..., 1, 1] * v[..., 1]
-    return (np.einsum("il,ij->lj", Dvv, vc1) - np.einsum("il,ji->jl", Dvv, vc0)) / metdet * rr
+    return _over_metdet(_da(Dvv, vc1) - _db(Dvv, vc0), metdet, rmetdet) * rr
+
+
+def ops_gradient_sphere_update(s, Dvv, Dinv, rr, old):
+    """K:271-312: grad_s += gradient_sphere(s)."""
+    return old + ops_gradient_sphere(s, Dvv, Dinv, rr)
+
+
+def ops_divergence_sphere_update(v, Dvv, Dinv, metdet, rr, old, alpha, beta, rmetdet=None):
+    """K:363-403: div_v = beta * div_v + alpha * divergence_sphere(v)."""
+    return beta * old + alpha * ops_divergence_sphere(v, Dvv, Dinv, metdet, rr, rmetdet)
 
 
 def ops_divergence_sphere_wk(v, Dvv, Dinv, spheremp, rr):
     t0 = spheremp * (Dinv[..., 0, 0] * v[..., 0] + Dinv[..., 0, 1] * v[..., 1])
     t1 = spheremp * (Dinv[..., 1, 0] * v[..., 0] + Dinv[..., 1, 1] * v[..., 1])
-    return -(np.einsum("mj,jn->mn", Dvv, t0) + np.einsum("nj,mj->mn", Dvv, t1)) * rr
+    return -(_wa(Dvv, t0) + _wb(Dvv, t1)) * rr
 
 
 def ops_laplace_tensor(s, Dvv, Dinv, spheremp, tensorVisc, rr):
@@ -171,21 +206,21 @@ def _cov_to_sphere(D, c0, c1, rr):
 
 def ops_curl_sphere_wk_testcov(s, Dvv, D, mp, rr):
     ms = mp * s
-    return _cov_to_sphere(D, -np.einsum("nj,mj->mn", Dvv, ms), np.einsum("mj,jn->mn", Dvv, ms), rr)
+    return _cov_to_sphere(D, -_wb(Dvv, ms), _wa(Dvv, ms), rr)
 
 
 def ops_grad_sphere_wk_testcov(s, Dvv, D, mp, metinv, metdet, rr):
     ms = mp * s
-    A = np.einsum("mj,jn->mn", Dvv, ms)
-    B = np.einsum("nj,mj->mn", Dvv, ms)
+    A = _wa(Dvv, ms)
+    B = _wb(Dvv, ms)
     c0 = -(metinv[..., 0, 0] * metdet * A + metinv[..., 1, 0] * metdet * B)
     c1 = -(metinv[..., 0, 1] * metdet * A + metinv[..., 1, 1] * metdet * B)
     return _cov_to_sphere(D, c0, c1, rr)
 
 
-def ops_vlaplace_sphere_wk_contra(v, Dvv, D, Dinv, mp, spheremp, metinv, metdet, nu_ratio, rr):
-    div = ops_divergence_sphere(v, Dvv, Dinv, metdet, rr) * nu_ratio
-    vort = ops_vorticity_sphere(v, Dvv, D, metdet, rr)
+def ops_vlaplace_sphere_wk_contra(v, Dvv, D, Dinv, mp, spheremp, metinv, metdet, nu_ratio, rr, rmetdet=None):
+    div = ops_divergence_sphere(v, Dvv, Dinv, metdet, rr, rmetdet) * nu_ratio
+    vort = ops_vorticity_sphere(v, Dvv, D, metdet, rr, rmetdet)
     return (2.0 * spheremp[..., None] * v * rr * rr + ops_grad_sphere_wk_testcov(div, Dvv, D, mp, metinv, metdet, rr)
             - ops_curl_sphere_wk_testcov(vort, Dvv, D, mp, rr))
 
@@ -197,3 +232,106 @@ def ops_vlaplace_sphere_wk_cartesian(v, Dvv, Dinv, spheremp, tensorVisc, s2c, rr
     if undamp_rr:
         out = out + 2.0 * spheremp[..., None] * v * rr * rr
     return out
+
+
+def ops_euler_step(vstar, qdp, qsize, qn0, dt, Dvv, Dinv, metdet, rr, rmetdet=None):
+    """EulerStepFunctor.hpp:32-68: qtens(q) = Qdp(qn0, q) - dt * divergence_sphere(vstar * Qdp(qn0, q)), q < qsize.
+    vstar [..., nlev, np, np, 2], qdp [..., qsize_d, 2, nlev, np, np], geometry [..., np, np](...) ->
+    qtens [..., qsize, nlev, np, np]."""
+    Q = qdp[..., :qsize, qn0, :, :, :]
+    flux = vstar[..., None, :, :, :, :] * Q[..., None]
+    lv = lambda a, k: a.reshape(a.shape[:a.ndim - k] + (1, 1) + a.shape[a.ndim - k:])  # noqa: E731  (over q, levels)
+    div = ops_divergence_sphere(flux, Dvv, lv(Dinv, 4), lv(metdet, 2), rr, None if rmetdet is None else lv(rmetdet, 2))
+    return Q - dt * div
+
+
+# HIP operator name (tinman_sandbox_amd.SPHERE_OPERATORS) -> (vector input, vector output, geometry it reads)
+OPS = {
+    "gradient_sphere": (False, True, ("Dinv",)),
+    "divergence_sphere": (True, False, ("Dinv", "metdet", "rmetdet")),
+    "vorticity_sphere": (True, False, ("D", "metdet", "rmetdet")),
+    "divergence_sphere_wk": (True, False, ("Dinv", "spheremp")),
+    "laplace_simple": (False, False, ("Dinv", "spheremp")),
+    "laplace_tensor": (False, False, ("Dinv", "spheremp", "tensorVisc")),
+    "laplace_tensor_replace": (False, False, ("Dinv", "spheremp", "tensorVisc")),
+    "curl_sphere_wk_testcov": (False, True, ("D", "mp")),
+    "grad_sphere_wk_testcov": (False, True, ("D", "mp", "metinv", "metdet")),
+    "vlaplace_sphere_wk_contra": (True, True, ("D", "Dinv", "mp", "spheremp", "metinv", "metdet", "rmetdet")),
+    "vlaplace_sphere_wk_cartesian": (True, True, ("Dinv", "spheremp", "tensorVisc", "vec_sph2cart")),
+    "vlaplace_sphere_wk_cartesian_damped": (True, True, ("Dinv", "spheremp", "tensorVisc", "vec_sph2cart")),
+    "gradient_sphere_update": (False, True, ("Dinv",)),
+    "divergence_sphere_update": (True, False, ("Dinv", "metdet", "rmetdet")),
+}
+
+
+def ops_apply(name, x, Dvv, geo, rr, old=None, alpha=1.0, beta=0.0, nu_ratio=1.0, use_rmetdet=True, dtype=np.float64):
+    """Operator `name` on x [ne][nlev][np][np](, 2) of the elements whose geometry is geo (dict of [ne][np][np]...
+    arrays, broadcast over levels), evaluated in `dtype`; `old` is what the *_update forms accumulate into.
+    use_rmetdet: the stored rmetdet multiplies (the kernels' form) instead of metdet dividing."""
+    f = lambda a: np.asarray(a, dtype=dtype)  # noqa: E731
+    x, Dvv, rr = f(x), f(Dvv), dtype(rr)
+    g = {k: f(geo[k])[:, None] for k in OPS[name][2]}
+    rmd = g.get("rmetdet") if use_rmetdet else None
+    if name == "gradient_sphere":
+        return ops_gradient_sphere(x, Dvv, g["Dinv"], rr)
+    if name == "gradient_sphere_update":
+        return ops_gradient_sphere_update(x, Dvv, g["Dinv"], rr, f(old))
+    if name == "divergence_sphere":
+        return ops_divergence_sphere(x, Dvv, g["Dinv"], g["metdet"], rr, rmd)
+    if name == "divergence_sphere_update":
+        return ops_divergence_sphere_update(x, Dvv, g["Dinv"], g["metdet"], rr, f(old), dtype(alpha), dtype(beta), rmd)
+    if name == "vorticity_sphere":
+        return ops_vorticity_sphere(x, Dvv, g["D"], g["metdet"], rr, rmd)
+    if name == "divergence_sphere_wk":
+        return ops_divergence_sphere_wk(x, Dvv, g["Dinv"], g["spheremp"], rr)
+    if name == "laplace_simple":
+        return ops_laplace_tensor(x, Dvv, g["Dinv"], g["spheremp"], None, rr)
+    if name in ("laplace_tensor", "laplace_tensor_replace"):
+        return ops_laplace_tensor(x, Dvv, g["Dinv"], g["spheremp"], g["tensorVisc"], rr)
+    if name == "curl_sphere_wk_testcov":
+        return ops_curl_sphere_wk_testcov(x, Dvv, g["D"], g["mp"], rr)
+    if name == "grad_sphere_wk_testcov":
+        return ops_grad_sphere_wk_testcov(x, Dvv, g["D"], g["mp"], g["metinv"], g["metdet"], rr)
+    if name == "vlaplace_sphere_wk_contra":
+        return ops_vlaplace_sphere_wk_contra(x, Dvv, g["D"], g["Dinv"], g["mp"], g["spheremp"], g["metinv"], g["metdet"],
+                                             dtype(nu_ratio), rr, rmd)
+    if name in ("vlaplace_sphere_wk_cartesian", "vlaplace_sphere_wk_cartesian_damped"):
+        return ops_vlaplace_sphere_wk_cartesian(x, Dvv, g["Dinv"], g["spheremp"], g["tensorVisc"], g["vec_sph2cart"], rr,
+                                                name == "vlaplace_sphere_wk_cartesian")
+    raise KeyError(name)
+
+
+# ---- the two stand-alone vertical integrals (caar_preq_hydrostatic / caar_preq_omega_ps) -------------------------
+# Vectorised over columns, a loop over levels in the reference's operation order (P:280-352 == oracle/caar_oracle.c
+# oracle_preq_*); numpy neither contracts a*b+c nor reassociates, so in float64 these are the reference's bits.
+# Fields [..., nlev, np, np], phis [..., np, np].
+def preq_hydrostatic(phis, Tv, p, dp, Rgas):
+    nlev = Tv.shape[-3]
+    phi = np.empty_like(Tv)
+    k = nlev - 1
+    hkk = 0.5 * dp[..., k, :, :] / p[..., k, :, :]                      # P:291
+    hkl = 2.0 * hkk
+    phii = Rgas * Tv[..., k, :, :] * hkl                                # P:293
+    phi[..., k, :, :] = phis + Rgas * Tv[..., k, :, :] * hkk            # P:294
+    for k in range(nlev - 2, -1, -1):
+        hkk = 0.5 * dp[..., k, :, :] / p[..., k, :, :]                  # P:300, P:308
+        hkl = 2.0 * hkk
+        phi[..., k, :, :] = phis + phii + Rgas * Tv[..., k, :, :] * hkk  # P:303, P:309
+        phii = phii + Rgas * Tv[..., k, :, :] * hkl                     # P:302
+    return phi
+
+
+def preq_omega_ps(p, vgrad_p, divdp):
+    nlev = p.shape[-3]
+    om = np.empty_like(p)
+    ckk = 0.5 / p[..., 0, :, :]                                         # P:323
+    term = divdp[..., 0, :, :]
+    om[..., 0, :, :] = vgrad_p[..., 0, :, :] / p[..., 0, :, :] - ckk * term  # P:325
+    suml = term
+    for k in range(1, nlev):
+        ckk = 0.5 / p[..., k, :, :]                                     # P:333, P:345
+        ckl = 2.0 * ckk
+        term = divdp[..., k, :, :]
+        om[..., k, :, :] = vgrad_p[..., k, :, :] / p[..., k, :, :] - ckl * suml - ckk * term  # P:336-337, P:348-349
+        suml = suml + term                                              # P:339
+    return om

@@ -151,6 +151,84 @@ def test_against_independent_numpy_statement(oracle, np_):
                                                               e["vec_sph2cart"], RR, bool(rr_term)))
 
 
+def _slab_close(got, want, tol=1e-15):
+    """max|got - want| <= tol * max|want| within every (element, level) slab of [ne][nlev]... arrays."""
+    ne, nl = want.shape[:2]
+    d = np.abs(got - want).reshape(ne, nl, -1).max(-1)
+    return bool(np.all(d <= tol * np.abs(want).reshape(ne, nl, -1).max(-1)))
+
+
+@pytest.mark.parametrize("np_", NPS)
+@pytest.mark.parametrize("use_rmetdet", (False, True))
+def test_batched_statement_matches_the_per_element_oracle(oracle, np_, use_rmetdet):
+    """np_oracle.ops_apply (the 80-bit truth of tests/test_operators_at_scale_gpu.py, here in fp64) on [ne][nlev] fields
+    with the geometry broadcast over levels equals the C oracle called one element and level at a time, to 1e-15 of
+    each slab's scale: the batching does not mix elements or levels.  Slabs of very different magnitude, elements
+    1..3 of a 5-element geometry; both ways of applying 1/metdet."""
+    Dvv = cases.dvv_for(np_, "double" if np_ == 4 else "gll")
+    g = geometry(np_, 5, 31)
+    e0, ne, nl = 1, 3, 6
+    ge = {k: v[e0:e0 + ne] for k, v in g.items()}
+    scale = 10.0 ** np.round(cases.uniform((ne, nl), 950, -6, 6))
+    for name, (vin, vout, _) in npo.OPS.items():
+        oname, okw = HIP_TO_ORACLE.get(name, (name, {}))
+        x = cases.uniform((ne, nl, np_, np_) + ((2,) if vin else ()), 951, -3, 5)
+        x *= scale.reshape((ne, nl) + (1,) * (x.ndim - 2))
+        old = cases.uniform((ne, nl, np_, np_) + ((2,) if vout else ()), 952, -1, 1)
+        old *= scale.reshape((ne, nl) + (1,) * (old.ndim - 2))
+        kw = dict(okw)
+        if name == "divergence_sphere_update":
+            kw.update(alpha=0.75, beta=-1.5)
+        if name in ("gradient_sphere_update", "divergence_sphere_update"):
+            kw["out"] = old
+        want = _oracle_all(oracle, oname, x, Dvv, g, e0, **dict(kw))
+        got = npo.ops_apply(name, x, Dvv, ge, RR, old=old, alpha=kw.get("alpha", 1.0), beta=kw.get("beta", 0.0),
+                            nu_ratio=kw.get("nu_ratio", 1.0), use_rmetdet=use_rmetdet)
+        assert got.shape == want.shape, name
+        assert _slab_close(got, want), (name, float(np.max(np.abs(got - want))))
+        # the long double statement agrees too (it is the same formulas)
+        got_ld = npo.ops_apply(name, x, Dvv, ge, RR, old=old, alpha=kw.get("alpha", 1.0), beta=kw.get("beta", 0.0),
+                               nu_ratio=kw.get("nu_ratio", 1.0), use_rmetdet=use_rmetdet, dtype=np.longdouble)
+        assert got_ld.dtype == np.longdouble and _slab_close(got_ld.astype(np.float64), want), name
+    # the Euler step: both time levels, fewer tracers than allocated
+    vstar = cases.uniform((ne, nl, np_, np_, 2), 953, -3, 5) * scale[..., None, None, None]
+    qdp = cases.uniform((ne, 3, 2, nl, np_, np_), 954, 0.5, 2.0)
+    for qn0 in (0, 1):
+        want = np.stack([po.euler_step(oracle, vstar[e], qdp[e], 2, qn0, 0.6, Dvv, ge["Dinv"][e], ge["metdet"][e], RR)
+                         for e in range(ne)])
+        got = npo.ops_euler_step(vstar, qdp, 2, qn0, 0.6, Dvv, ge["Dinv"], ge["metdet"], RR,
+                                 rmetdet=ge["rmetdet"] if use_rmetdet else None)
+        assert got.shape == want.shape == (ne, 2, nl, np_, np_)
+        assert _slab_close(got.reshape(ne * 2, nl, np_, np_), want.reshape(ne * 2, nl, np_, np_)), qn0
+
+
+@pytest.mark.parametrize("np_,nlev", [(4, 2), (4, 3), (8, 2), (4, 72), (8, 128)])
+def test_numpy_vertical_integrals_are_bit_identical_to_the_oracle(oracle, np_, nlev):
+    """np_oracle.preq_hydrostatic / preq_omega_ps (vectorised over columns) give oracle_preq_*'s bits: they are the
+    reference's operation order, so the GPU tests may hold the kernels bit-identical to them at any size."""
+    import ctypes as C
+    ne = 3
+    phis = cases.uniform((ne, np_, np_), 960, 0, 3e4)
+    Tv = cases.uniform((ne, nlev, np_, np_), 961, 200, 310)
+    p = np.cumsum(cases.uniform((ne, nlev, np_, np_), 962, 500, 1500), axis=1)
+    dp = cases.uniform((ne, nlev, np_, np_), 963, 500, 1500)
+    vg = cases.uniform((ne, nlev, np_, np_), 964, -50, 50)
+    dd = cases.uniform((ne, nlev, np_, np_), 965, -5, 5)
+    P = po._ptr
+    oracle.lib.oracle_preq_hydrostatic.argtypes = [C.c_int, C.c_int] + [po._dp] * 4 + [C.c_double, po._dp]
+    oracle.lib.oracle_preq_omega_ps.argtypes = [C.c_int, C.c_int] + [po._dp] * 4
+    phi_w, om_w = np.zeros_like(Tv), np.zeros_like(Tv)
+    for e in range(ne):
+        out = np.zeros((nlev, np_, np_))
+        oracle.lib.oracle_preq_hydrostatic(np_, nlev, P(phis[e]), P(Tv[e]), P(p[e].copy()), P(dp[e]), 287.04, P(out))
+        phi_w[e] = out
+        out = np.zeros((nlev, np_, np_))
+        oracle.lib.oracle_preq_omega_ps(np_, nlev, P(p[e].copy()), P(vg[e]), P(dd[e]), P(out))
+        om_w[e] = out
+    assert np.array_equal(npo.preq_hydrostatic(phis, Tv, p, dp, 287.04), phi_w)
+    assert np.array_equal(npo.preq_omega_ps(p, vg, dd), om_w)
+
+
 def test_polynomial_exactness_of_the_weak_laplacian(oracle):
     """On a flat, unit-metric element (D = Dinv = I, metdet = 1, spheremp = GLL weights w_a w_b) the weak
     Laplacian of a polynomial that vanishes with its normal derivative at the element edge is the mass-weighted
