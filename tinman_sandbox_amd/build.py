@@ -15,7 +15,7 @@ HOST = os.path.join(HERE, "host")
 LIB = os.path.join(CSRC, "libcaar_hip.so")
 ARCH = "gfx950"
 
-HIP_SOURCES = ["caar_np4.hip", "caar_np4_steps.hip", "caar_np8.hip", "caar_abi.hip", "caar_norms.hip", "caar_layout.hip", "caar_operators.hip", "caar_operators_ex.hip", "caar_alloc.hip", "caar_membench.hip"]
+HIP_SOURCES = ["caar_np4.hip", "caar_np4_steps.hip", "caar_np8.hip", "caar_abi.hip", "caar_norms.hip", "caar_layout.hip", "caar_operators.hip", "caar_operators_ex.hip", "caar_alloc.hip", "caar_membench.hip", "caar_f90.hip"]
 
 
 def hipcc():
@@ -127,6 +127,29 @@ def build_fortran_driver(force=False, verbose=False):
     return exe
 
 
+def build_fortran_resident(force=False, verbose=False):
+    """Fortran host example whose arrays stay on the device in Fortran order (host/fortran/caar_f90_resident.F90):
+    caar_mod + caar_device_mod (caar_launch_f90, caar_arrays_alloc, the HIP calls it needs), linked against libcaar_hip.so
+    and the HIP runtime.  None when flang is missing."""
+    fdir = os.path.join(HOST, "fortran")
+    if not os.path.exists(FLANG):
+        return None
+    out = os.path.join(fdir, "build")
+    exe = os.path.join(out, "caar_f90_resident")
+    srcs = [os.path.join(fdir, f) for f in ("caar_mod.F90", "caar_device_mod.F90", "caar_f90_resident.F90")]
+    if force or _stale(exe, srcs + [LIB]):
+        # (a module directory of its own: caar_f90_driver's build writes caar_mod.mod as well)
+        mods = os.path.join(out, "resident_mod")
+        os.makedirs(mods, exist_ok=True)
+        cmd = [FLANG, "-O2", "-module-dir", mods] + srcs + ["-L" + CSRC, "-lcaar_hip", "-L/opt/rocm/lib", "-lamdhip64",
+                                                           "-Wl,-rpath,$ORIGIN/../../../csrc", "-Wl,-rpath,/opt/rocm/lib",
+                                                           "-o", exe]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.run(cmd, check=True, cwd=mods, capture_output=not verbose)
+    return exe
+
+
 def build_all(force=False, verbose=False, debug=True):
     lib = build_library(force, verbose)
     if debug:
@@ -135,6 +158,7 @@ def build_all(force=False, verbose=False, debug=True):
     for np_, nlev in ((4, 72), (4, 128), (8, 72)):
         build_host_driver(force, verbose, np_, nlev)
     build_fortran_driver(force, verbose)
+    build_fortran_resident(force, verbose)
     return lib
 
 

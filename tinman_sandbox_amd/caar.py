@@ -120,7 +120,9 @@ class CaarLibrary:
         "caar_arrays_placement", "caar_create_ex", "caar_stream_copy", "caar_stream_copy_tuned",
         "caar_stream_copy_tuned_variants", "caar_stream_copy_tuned_info", "caar_traffic_skeleton", "caar_time_runs",
         "caar_reciprocal", "caar_debug_dp3d_violations")
-    SYMBOLS = BOUNDARY_SYMBOLS + TUNING_SYMBOLS
+    # include/caar_f90.h: compute_and_apply_rhs on Fortran-ordered device arrays — additive, not part of the frozen boundary
+    F90_SYMBOLS = ("caar_launch_f90", "caar_launch_steps_f90")
+    SYMBOLS = BOUNDARY_SYMBOLS + TUNING_SYMBOLS + F90_SYMBOLS
 
     def __init__(self, path=LIB_PATH):
         if not os.path.exists(path):
@@ -145,6 +147,9 @@ class CaarLibrary:
                                   C.POINTER(_CaarParams), vp]
         L.caar_launch_steps.argtypes = [C.POINTER(_CaarDims), C.POINTER(_CaarArrays), vp, C.POINTER(_CaarParams), C.c_int,
                                         C.c_int, vp]
+        L.caar_launch_f90.argtypes = [C.POINTER(_CaarDims), C.POINTER(_CaarArrays), vp, C.POINTER(_CaarParams), vp]
+        L.caar_launch_steps_f90.argtypes = [C.POINTER(_CaarDims), C.POINTER(_CaarArrays), vp, C.POINTER(_CaarParams), C.c_int,
+                                            C.c_int, vp]
         L.caar_launch_state_norms.argtypes = [C.POINTER(_CaarDims), C.POINTER(_CaarArrays), C.c_int,
                                               C.c_int, C.c_int, vp, vp]
         L.caar_sphere_operator.argtypes = [C.POINTER(_CaarDims), C.POINTER(_CaarArrays), vp, C.c_int, C.c_int,

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/caar.h"
+#include "../../include/caar_f90.h"
 #include "../../include/caar_tuning.h"
 #include "caar_kernel_args.h"
 #include "caar_window_tuner.h"
@@ -52,6 +53,12 @@ hipError_t launch_layout_all(int np, int count, double* const* dst, const double
                              const int* qdp_outer, int nlev, int qd, bool to_caar, hipStream_t s);
 hipError_t launch_traffic_skeleton(const KernelArgs& k, int nlev, int variant, int num_elems, hipStream_t stream);
 hipError_t launch_traffic_skeleton_np8(const KernelArgs& k, int nlev, int variant, int num_elems, hipStream_t stream);
+// caar_f90.hip: the Fortran-order kernel of (np, nlev) (launch == nullptr: none)
+struct F90Kernel {
+  hipError_t (*launch)(const KernelArgs&, int num_elems, hipStream_t stream);
+  bool prefers_xcd_chunked;
+};
+F90Kernel f90_kernel(int np, int nlev);
 #ifdef CAAR_DEBUG
 long long debug_dp3d_count_np4(int reset);
 long long debug_dp3d_count_np4_steps(int reset);
@@ -551,22 +558,33 @@ int caar_launch(const CaarDims* dims, const CaarArrays* dev, const double* dvv_d
   return launch_with(dims, dev, dvv_dev, p, stream, nullptr);
 }
 
-// forced != nullptr: the tuning knobs the caller already read (a graph capture bakes ONE choice into all of
-// its launches and into its cache key)
-static int launch_with(const CaarDims* dims, const CaarArrays* dev, const double* dvv_dev, const CaarParams* p,
-                       void* stream, const caar::LaunchChoice* forced, bool tune) {
+// The checks of every single-call launch (caar_launch, caar_launch_f90), all before any HIP call.  pairs16: v and vn0 are
+// moved as 16-byte (u, v) pairs (the C++ layout; in Fortran order u and v are 8-byte values a plane apart).
+static int check_launch(const CaarDims* dims, const CaarArrays* dev, const double* dvv_dev, const CaarParams* p, bool pairs16,
+                        const caar::Config** cfg_out) {
   int rc = check_common(dims, p);
   if (rc) return rc;
   if (!dev || !dvv_dev) return CAAR_EINVAL;
   for (int i = 0; i < CAAR_NUM_ARRAYS; ++i)
     if (!*array_slot(dev, i)) return CAAR_EINVAL;
   // the kernels move v and vn0 as 16-byte (u, v) pairs and everything else as 8-byte doubles
-  if (((size_t)dev->elem_state_v | (size_t)dev->elem_derived_vn0) & 15) return CAAR_EINVAL;
+  if (pairs16 && (((size_t)dev->elem_state_v | (size_t)dev->elem_derived_vn0) & 15)) return CAAR_EINVAL;
   for (int i = 0; i < CAAR_NUM_ARRAYS; ++i)
     if ((size_t)*array_slot(dev, i) & 7) return CAAR_EINVAL;
   const caar::Config* cfg = caar::find_config(dims->np, dims->nlev);
   if (!cfg) return CAAR_EUNSUPPORTED;
   if (!caar_supported_ex(dims->np, dims->nlev, p->rsplit)) return CAAR_EUNSUPPORTED;  // (before anything is enqueued)
+  *cfg_out = cfg;
+  return CAAR_OK;
+}
+
+// forced != nullptr: the tuning knobs the caller already read (a graph capture bakes ONE choice into all of
+// its launches and into its cache key)
+static int launch_with(const CaarDims* dims, const CaarArrays* dev, const double* dvv_dev, const CaarParams* p,
+                       void* stream, const caar::LaunchChoice* forced, bool tune) {
+  const caar::Config* cfg = nullptr;
+  const int rc = check_launch(dims, dev, dvv_dev, p, true, &cfg);
+  if (rc) return rc;
   if (p->rsplit == 0 && (!p->hybi_dev || ((size_t)p->hybi_dev & 7))) return CAAR_EINVAL;
   const int n = p->nete - p->nets;
   if (n == 0) return CAAR_OK;
@@ -626,6 +644,53 @@ int caar_launch_steps(const CaarDims* dims, const CaarArrays* dev, const double*
   CaarParams q = *p;
   for (int i = 0; i < nsteps && rc == CAAR_OK; ++i) {
     rc = launch_with(dims, dev, dvv_dev, &q, stream, &ch);
+    if (rotate) {  // data_structures.cpp:174-180
+      const int t = q.np1;
+      q.np1 = q.nm1;
+      q.nm1 = q.n0;
+      q.n0 = t;
+    }
+  }
+  return rc;
+}
+
+// ---- Fortran-ordered arrays (include/caar_f90.h) ----------------------------------------------------------------
+// The kernel for (np, nlev) of caar_f90.hip, validated like caar_launch (check_launch).  The knobs: the cache window as
+// caar_launch reads it (no adaptive tuning) and the element mapping the C++-layout twin was measured fastest with, unless the
+// host fixed it (caar_set_xcd_chunked).  `forced`: caar_launch_steps_f90 reads them once for all its launches.
+static int launch_f90_with(const CaarDims* dims, const CaarArrays* f90_dev, const double* dvv_dev, const CaarParams* p,
+                           void* stream, const caar::LaunchChoice* forced) {
+  const caar::Config* cfg = nullptr;
+  const int rc = check_launch(dims, f90_dev, dvv_dev, p, false, &cfg);
+  if (rc) return rc;
+  const caar::F90Kernel fk = caar::f90_kernel(dims->np, dims->nlev);
+  if (p->rsplit == 0 || !fk.launch) return CAAR_EUNSUPPORTED;  // no Fortran-order form of the Eulerian branch
+  const int n = p->nete - p->nets;
+  if (n == 0) return CAAR_OK;
+  caar::LaunchChoice ch = forced ? *forced : caar::launch_choice(nullptr);
+  if (!forced) {
+    const int x = g_xcd_chunked.load(std::memory_order_relaxed);
+    ch.xcd_chunked = x < 0 ? (fk.prefers_xcd_chunked ? 1 : 0) : x;
+  }
+  caar::KernelArgs k;
+  fill_args_impl(k, dims, f90_dev, dvv_dev, p, ch);
+  return (int)fk.launch(k, n, (hipStream_t)stream);
+}
+
+int caar_launch_f90(const CaarDims* dims, const CaarArrays* f90_dev, const double* dvv_dev, const CaarParams* p, void* stream) {
+  return launch_f90_with(dims, f90_dev, dvv_dev, p, stream, nullptr);
+}
+
+int caar_launch_steps_f90(const CaarDims* dims, const CaarArrays* f90_dev, const double* dvv_dev, const CaarParams* p,
+                          int nsteps, int rotate, void* stream) {
+  if (!dims || !p || nsteps < 1) return CAAR_EINVAL;
+  caar::LaunchChoice ch = caar::launch_choice(nullptr);
+  const int x = g_xcd_chunked.load(std::memory_order_relaxed);
+  ch.xcd_chunked = x < 0 ? (caar::f90_kernel(dims->np, dims->nlev).prefers_xcd_chunked ? 1 : 0) : x;
+  CaarParams q = *p;
+  int rc = CAAR_OK;
+  for (int i = 0; i < nsteps && rc == CAAR_OK; ++i) {
+    rc = launch_f90_with(dims, f90_dev, dvv_dev, &q, stream, &ch);
     if (rotate) {  // data_structures.cpp:174-180
       const int t = q.np1;
       q.np1 = q.nm1;

@@ -140,6 +140,27 @@ __device__ __forceinline__ void stream_store(T* p, T v) {
   else *p = v;
 }
 
+// The (u, v) pair of a point of a Fortran-ordered vector field (v, vn0: (np, np, 2, nlev, ...)): a level holds a u plane and
+// then a v plane of PLANE = np*np doubles, so the pair is two 8-byte accesses PLANE doubles apart (each still covers whole
+// 128 B lines per wave instruction).  `base`: the wave's first pair in the C++ layout (the same byte in both orders); `i`:
+// this lane's u offset from there, in doubles — ONE unsigned index, as the C++ form's `r * 64 + ulane`, so that the access
+// stays scalar base + 32-bit lane offset + immediate (with the tile offset added separately, the tiles beyond the 4 KiB
+// immediate range got 64-bit per-lane addresses: 2-6 more VGPRs).  Only 8-byte alignment is assumed.
+template <bool NT, int PLANE>
+__device__ __forceinline__ dbl2 f90_pair_load(const dbl2* base, unsigned i) {
+  const double* p = reinterpret_cast<const double*>(base) + i;
+  dbl2 x;
+  x.x = stream_load<NT>(p);
+  x.y = stream_load<NT>(p + PLANE);
+  return x;
+}
+template <bool NT, int PLANE>
+__device__ __forceinline__ void f90_pair_store(dbl2* base, unsigned i, dbl2 x) {
+  double* p = reinterpret_cast<double*>(base) + i;
+  stream_store<NT>(p, (double)x.x);
+  stream_store<NT>(p + PLANE, (double)x.y);
+}
+
 // Pointer for RE-READING values a kernel parked in LDS to free registers.  The compiler must not replace such a read by the
 // register copy of what was stored (that is the point of parking), so the address is laundered through an empty asm; the
 // access stays a plain ds_read_b64 in the LDS address space.  (A `volatile` generic pointer does the job too, but compiles to

@@ -175,7 +175,11 @@ struct Np4N0In {
 // call's n0 state (dp3d, u, v, T), 2 = lds.carry holds its nm1 state, 4 = lds.carry holds its tracer block (2 and 4 only
 // with CARRY_LDS), 8 = lds.carry holds the accumulators and pecnd, and the metric terms are still staged (CARRY_LDS == 2).
 // Every STEPS call hands the same things on to the next one.
-template <int NLEV_T, int TPW, int MINW, bool MOIST, bool SNT, bool ANT, int PF, bool PERSIST, bool ETA_COND, bool VADV, int DYNW, int PARK = 0, bool STEPS = false, int CARRY_LDS = 0, int CARRY_IN = 0, int STORES = -1, int WAVES = 0>
+// F90: the element arrays are in Fortran order (include/caar_f90.h, caar_f90.hip): point (a, b) of a level sits at a + 4b
+// instead of 4a + b, v and vn0 hold a u plane and a v plane per level, D / Dinv four (np, np) planes, and Qdp's tracer slots
+// are (q, t) instead of (t, q).  Each lane keeps its point: only the addresses of the global accesses change (a tile is the
+// same contiguous 512 B / 1 KiB block in both orders); the MFMA operands, the scans and everything staged in LDS do not.
+template <int NLEV_T, int TPW, int MINW, bool MOIST, bool SNT, bool ANT, int PF, bool PERSIST, bool ETA_COND, bool VADV, int DYNW, int PARK = 0, bool STEPS = false, int CARRY_LDS = 0, int CARRY_IN = 0, int STORES = -1, int WAVES = 0, bool F90 = false>
 __device__ __forceinline__ void caar_np4_element(const KernelArgs& k, Np4Lds<NLEV_T, TPW, PERSIST, VADV, DYNW, PARK, CARRY_LDS>& lds,
                                                  Np4N0In<TPW>* carry = nullptr, int step_stores = 3, int tot_par = 0,
                                                  long long ie_known = -2) {
@@ -251,6 +255,10 @@ __device__ __forceinline__ void caar_np4_element(const KernelArgs& k, Np4Lds<NLE
   // a compile-time tile number and ulane an UNSIGNED lane id, so each access is one
   // global_load/store with scalar base, one shared 32-bit lane offset and an immediate.
   const unsigned ulane = sub * 16 + pt;  // this lane's offset inside a tile of the layout [lev][a][b]
+  // ... of the arrays in memory (F90: (np, np, lev): point a + 4b), and of its u inside a tile of v / vn0 (F90 only: two
+  // planes of 16 per level, v 16 doubles after u)
+  const unsigned glane = F90 ? sub * 16 + ((lane >> 4) + 4 * (lane & 3)) : ulane;
+  const unsigned vlane = F90 ? sub * 32 + ((lane >> 4) + 4 * (lane & 3)) : 0u;
   // (the even shapes keep the expression they always had: the headline kernels' code must not change with this option)
   const size_t wbase = UNEVEN ? (size_t)tile0 * 64 : (size_t)w * (TPW * 64);  // first point of this wave's tiles inside a field block
 
@@ -264,22 +272,25 @@ __device__ __forceinline__ void caar_np4_element(const KernelArgs& k, Np4Lds<NLE
   // n0 inputs of this wave's tiles
   using N0In = Np4N0In<TPW>;
   static_assert(!STEPS || (!PERSIST && !RAGGED && !VADV), "step loop: plain Lagrangian form");
+  static_assert(!F90 || (!STEPS && !PERSIST && !VADV), "Fortran order: the single-call vertically Lagrangian form");
   auto load_n0 = [&](size_t ie) {
     const double* __restrict__ dp_n0 = k.dp3d + (ie * tl + k.n0) * BLK + wbase;
     const dbl2* __restrict__ v_n0 = reinterpret_cast<const dbl2*>(k.v + (ie * tl + k.n0) * BLK * 2) + wbase;
     const double* __restrict__ T_n0 = k.T + (ie * tl + k.n0) * BLK + wbase;
-    const double* __restrict__ Qdp = k.Qdp + ((ie * k.qsize_d + 0) * 2 + (MOIST ? k.qn0 : 0)) * BLK + wbase;
+    // the first tracer at slot qn0: C++ [ie][q][t] (t fastest), Fortran (q, t, ie) (q fastest)
+    const double* __restrict__ Qdp = k.Qdp + (F90 ? (ie * 2 + (MOIST ? k.qn0 : 0)) * k.qsize_d + 0
+                                                  : (ie * k.qsize_d + 0) * 2 + (MOIST ? k.qn0 : 0)) * BLK + wbase;
     N0In x;
 #pragma unroll
     for (int r = 0; r < TPW; ++r) {
       x.dp[r] = x.u[r] = x.v[r] = x.T[r] = x.q[r] = 0.0;
       if (CAAR_LIVE(r)) {
-        x.dp[r] = stream_load<SNT>(dp_n0 + r * 64 + ulane);
-        const dbl2 uv = stream_load<SNT>(v_n0 + r * 64 + ulane);
+        x.dp[r] = stream_load<SNT>(dp_n0 + r * 64 + glane);
+        const dbl2 uv = F90 ? f90_pair_load<SNT, PP>(v_n0, r * 128 + vlane) : stream_load<SNT>(v_n0 + r * 64 + ulane);
         x.u[r] = uv.x;
         x.v[r] = uv.y;
-        x.T[r] = stream_load<SNT>(T_n0 + r * 64 + ulane);
-        x.q[r] = MOIST ? stream_load<SNT>(Qdp + r * 64 + ulane) : 0.0;
+        x.T[r] = stream_load<SNT>(T_n0 + r * 64 + glane);
+        x.q[r] = MOIST ? stream_load<SNT>(Qdp + r * 64 + glane) : 0.0;
       }
     }
     return x;
@@ -287,6 +298,19 @@ __device__ __forceinline__ void caar_np4_element(const KernelArgs& k, Np4Lds<NLE
 
   // address of the idx-th entry of an element's LDS metric image (G_* layout)
   auto geo_src = [&](size_t ie, int idx) -> const double* {
+    if constexpr (F90) {  // the same image from Fortran-ordered arrays: (np, np) planes; D, Dinv (np, np, 2, 2)
+      if (idx < G_D) {
+        const int i = idx & (PP - 1), fi = (i >> 2) + 4 * (i & 3);  // point 4a + b sits at a + 4b
+        if (idx < G_SPHEREMP) return k.fcor + ie * PP + fi;
+        if (idx < G_METDET) return k.spheremp + ie * PP + fi;
+        if (idx < G_RMETDET) return k.metdet + ie * PP + fi;
+        if (idx < G_PHIS) return k.rmetdet + ie * PP + fi;
+        return k.phis + ie * PP + fi;
+      }
+      // image entry [pt][r][c] (pt = 4a + b) is (a, b, r, c): plane r + 2c, offset a + 4b
+      const int i = (idx - G_D) & (4 * PP - 1), p4 = i >> 2, r = (i >> 1) & 1, c = i & 1;
+      return (idx < G_DINV ? k.D : k.Dinv) + ie * PP * 4 + (r + 2 * c) * PP + (p4 >> 2) + 4 * (p4 & 3);
+    }
     if (idx < G_SPHEREMP) return k.fcor + ie * PP + idx;
     if (idx < G_METDET) return k.spheremp + ie * PP + (idx - G_SPHEREMP);
     if (idx < G_RMETDET) return k.metdet + ie * PP + (idx - G_METDET);
@@ -379,14 +403,14 @@ __device__ __forceinline__ void caar_np4_element(const KernelArgs& k, Np4Lds<NLE
       double Tnm1, dpnm1, om, pec, eta;
     };
     auto load_tile = [&](int r) {
-      const unsigned off = r * 64 + ulane;
+      const unsigned off = r * 64 + glane;
       TileIn x = {};
       if (!CAAR_LIVE(r)) return x;
       if (CARRY_LDS && (carry_flags & 2)) {
         // the previous call parked its n0 state (this call's nm1) in LDS: it is read where it is used, not a tile ahead
         // (LDS latency needs no prefetch, and four values fewer are live per tile in flight)
       } else {
-        x.vnm1 = stream_load<SNT>(v_nm1 + off);
+        x.vnm1 = F90 ? f90_pair_load<SNT, PP>(v_nm1, r * 128 + vlane) : stream_load<SNT>(v_nm1 + off);
         x.Tnm1 = stream_load<SNT>(T_nm1 + off);
         x.dpnm1 = stream_load<SNT>(dp_nm1 + off);
       }
@@ -404,7 +428,7 @@ __device__ __forceinline__ void caar_np4_element(const KernelArgs& k, Np4Lds<NLE
           x.eta = eta_rmw ? stream_load<ANT>(eta + off) : 0.0;
         }
       } else {
-        x.vn0 = stream_load<ANT>(vn0 + off);
+        x.vn0 = F90 ? f90_pair_load<ANT, PP>(vn0, r * 128 + vlane) : stream_load<ANT>(vn0 + off);
         x.om = stream_load<ANT>(omega_p + off);
         x.pec = stream_load<SNT>(pecnd + off);
         x.eta = eta_rmw ? stream_load<ANT>(eta + off) : 0.0;
@@ -548,7 +572,7 @@ __device__ __forceinline__ void caar_np4_element(const KernelArgs& k, Np4Lds<NLE
     for (int rr = 0; rr < TPW; ++rr) {
       const int r = TPW - 1 - rr;  // bottom tile of the wave first: `below` accumulates upwards
       const int t = CAAR_TILE(r);
-      const unsigned off = r * 64 + ulane;
+      const unsigned off = r * 64 + glane;
       TileIn nxt = cur;
       if (r > 0) nxt = PF ? pre[r - 1] : load_tile(r - 1);
       if constexpr (UNEVEN) {
@@ -651,7 +675,10 @@ __device__ __forceinline__ void caar_np4_element(const KernelArgs& k, Np4Lds<NLE
       const bool st_state = !STEPS || (st_mask & 1), st_phi = !STEPS || (st_mask & 2);
       const bool st_acc = CARRY_LDS < 2 || (st_mask & 4);  // accumulators carried in LDS: only the last call's reach memory
       const bool st_eta = CARRY_LDS != 2 ? true : st_acc;    // (3: eta_dot_dpdn is not carried)
-      if (st_state) stream_store<SNT>(v_np1 + off, vo);
+      if (st_state) {
+        if constexpr (F90) f90_pair_store<SNT, PP>(v_np1, r * 128 + vlane, vo);
+        else stream_store<SNT>(v_np1 + off, vo);
+      }
       const double T_new = spheremp * (Tnm1 + k.dt2 * ttens);                         // P:253
       if (st_state) stream_store<SNT>(T_np1 + off, T_new);
       const double dp_new = VADV ? spheremp * (dpnm1 - k.dt2 * (divdp_r + eta_hi - eta_lo))   // X:515-517
@@ -664,7 +691,10 @@ __device__ __forceinline__ void caar_np4_element(const KernelArgs& k, Np4Lds<NLE
       dbl2 vn;
       vn.x = cur.vn0.x + k.eta_ave_w * (u_r * dp[r]);               // P:117
       vn.y = cur.vn0.y + k.eta_ave_w * (v_r * dp[r]);               // P:118
-      if (st_acc) stream_store<ANT>(vn0 + off, vn);
+      if (st_acc) {
+        if constexpr (F90) f90_pair_store<ANT, PP>(vn0, r * 128 + vlane, vn);
+        else stream_store<ANT>(vn0 + off, vn);
+      }
       {
         const double e_new = cur.eta + (VADV ? k.eta_ave_w * eta_lo : eta_zero);  // P:172, X:271-272
         // ETA_COND: the update adds eta_ave_w * 0 (vertically Lagrangian), so the stored value

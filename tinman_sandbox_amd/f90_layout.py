@@ -7,7 +7,8 @@ indices coincide with the C++ layout (C++ [a][b][c] == Fortran (a+1,b+1,c+1), SU
 so the conversion is an axis permutation; on the device it is done by
 csrc/caar_layout.hip (caar_layout_from_f90 / caar_layout_to_f90), on host arrays by the
 numpy views below (used for staging small data and as the definition the kernels are
-tested against)."""
+tested against).  compute_and_apply_rhs / compute_and_apply_rhs_steps run the routine on such arrays in
+place (include/caar_f90.h: caar_launch_f90 / caar_launch_steps_f90), with no conversion at all."""
 import ctypes as C
 
 import numpy as np
@@ -70,6 +71,22 @@ class F90Arrays:
         self.t = tensors
 
     @classmethod
+    def allocate(cls, np_, nlev, num_elems, qsize_d=1, timelevels=3, device="cuda", place=None):
+        """Zeroed arrays from the library's allocator (caar_arrays_alloc_ex: placed for bandwidth like ElementArrays'):
+        caar_array_len is the same in both orders, so the 16 buffers hold the Fortran-ordered arrays as they are.
+        `place`: a caar.placement(...) or None for the library's default."""
+        dev = torch.device(device)
+        idx = dev.index if dev.index is not None else torch.cuda.current_device()
+        shapes = f90_shapes(np_, nlev, qsize_d, timelevels, num_elems)
+        with torch.cuda.device(idx):
+            arena = _c._Arena(_c._CaarDims(np_, nlev, qsize_d, timelevels, num_elems), idx, place)
+            tensors = {}
+            for n in _c.ARRAY_NAMES:
+                ptr = C.cast(getattr(arena.ptrs, n), C.c_void_p).value
+                tensors[n] = torch.as_tensor(_c._ArenaView(arena, ptr, shapes[n]), device=torch.device("cuda", idx)).zero_()
+        return cls(np_, nlev, num_elems, qsize_d, timelevels, torch.device("cuda", idx), tensors)
+
+    @classmethod
     def from_numpy(cls, f90, np_, nlev, ne, qsize_d=1, timelevels=3, device="cuda"):
         return cls(np_, nlev, ne, qsize_d, timelevels, device,
                    {n: torch.from_numpy(np.ascontiguousarray(f90[n])).to(device) for n in _c.ARRAY_NAMES})
@@ -79,6 +96,9 @@ class F90Arrays:
 
     def pointers(self):
         return _c._CaarArrays(*[C.cast(self.t[n].data_ptr(), _c._dp) for n in _c.ARRAY_NAMES])
+
+    def dims(self):
+        return _c._CaarDims(self.np, self.nlev, self.qsize_d, self.timelevels, self.num_elems)
 
 
 def ingest(f90, arrays, e0=0, e1=None, stream=None):
@@ -101,3 +121,41 @@ def egress(arrays, f90, e0=0, e1=None, all_arrays=False, stream=None):
     dims, src, dst = arrays.dims(), arrays.pointers(), f90.pointers()
     L.check(L.lib.caar_layout_to_f90(C.byref(dims), C.byref(src), C.byref(dst), e0, e1, int(all_arrays),
                                      C.c_void_p(stream.cuda_stream)), "caar_layout_to_f90")
+
+
+def _f90_call(f90, data_or_params, stream):
+    """(dims, pointers, CaarParams, device Dvv, stream) of one call on the Fortran-ordered `f90`.  `data_or_params`: a
+    TestData (its control, constants, hvcoord and deriv are read as by caar.compute_and_apply_rhs; its arrays are not
+    touched) or a (CaarParams, device Dvv tensor) pair."""
+    _c._require_gpu(f90)
+    if isinstance(data_or_params, tuple):
+        prm, dvv = data_or_params
+    else:
+        prm, dvv = data_or_params.params(device_constants=True), data_or_params.dvv_device()
+    stream = stream or torch.cuda.current_stream(f90.device)
+    return f90.dims(), f90.pointers(), prm, dvv, stream
+
+
+def compute_and_apply_rhs(f90, data_or_params, stream=None):
+    """Homme::compute_and_apply_rhs on Fortran-ordered device arrays, in place (caar_launch_f90): one asynchronous launch
+    on `stream` (default: torch's current stream) over the elements [nets, nete) of the scalars' Control."""
+    L = _c.library()
+    dims, ptrs, prm, dvv, stream = _f90_call(f90, data_or_params, stream)
+    with torch.cuda.device(f90.device):
+        rc = L.lib.caar_launch_f90(C.byref(dims), C.byref(ptrs), C.c_void_p(dvv.data_ptr()), C.byref(prm),
+                                   C.c_void_p(stream.cuda_stream))
+    L.check(rc, "caar_launch_f90")
+
+
+def compute_and_apply_rhs_steps(f90, data_or_params, nsteps, rotate=True, stream=None):
+    """`nsteps` calls with TestData::update_time_levels between them (caar_launch_steps_f90).  Given a TestData, it leaves
+    its control rotated nsteps times, like the loop it replaces (caar.compute_and_apply_rhs_steps)."""
+    L = _c.library()
+    dims, ptrs, prm, dvv, stream = _f90_call(f90, data_or_params, stream)
+    with torch.cuda.device(f90.device):
+        rc = L.lib.caar_launch_steps_f90(C.byref(dims), C.byref(ptrs), C.c_void_p(dvv.data_ptr()), C.byref(prm), nsteps,
+                                         1 if rotate else 0, C.c_void_p(stream.cuda_stream))
+    L.check(rc, "caar_launch_steps_f90")
+    if rotate and not isinstance(data_or_params, tuple):
+        for _ in range(nsteps):
+            data_or_params.update_time_levels()
