@@ -15,7 +15,7 @@ HOST = os.path.join(HERE, "host")
 LIB = os.path.join(CSRC, "libcaar_hip.so")
 ARCH = "gfx950"
 
-HIP_SOURCES = ["caar_np4.hip", "caar_np4_steps.hip", "caar_np8.hip", "caar_abi.hip", "caar_norms.hip", "caar_layout.hip", "caar_operators.hip", "caar_operators_ex.hip", "caar_alloc.hip", "caar_membench.hip", "caar_f90.hip"]
+HIP_SOURCES = ["caar_np4.hip", "caar_np4_steps.hip", "caar_np8.hip", "caar_abi.hip", "caar_norms.hip", "caar_layout.hip", "caar_operators.hip", "caar_operators_ex.hip", "caar_alloc.hip", "caar_membench.hip", "caar_f90.hip", "caar_dss.hip"]
 
 
 def hipcc():
@@ -50,7 +50,8 @@ def build_library(force=False, verbose=False, jobs=4, debug=False, extra=False):
     counter, include/caar.h caar_debug_dp3d_violations); the other objects are the release ones."""
     from concurrent.futures import ThreadPoolExecutor
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [
-        os.path.join(HERE, "..", "include", "caar.h"), os.path.join(HERE, "..", "include", "caar_tuning.h")]
+        os.path.join(HERE, "..", "include", "caar.h"), os.path.join(HERE, "..", "include", "caar_tuning.h"),
+        os.path.join(HERE, "..", "include", "caar_dss.h")]
     objdir = os.path.join(CSRC, "build")
     os.makedirs(objdir, exist_ok=True)
     flags = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"]

@@ -122,7 +122,9 @@ class CaarLibrary:
         "caar_reciprocal", "caar_debug_dp3d_violations")
     # include/caar_f90.h: compute_and_apply_rhs on Fortran-ordered device arrays — additive, not part of the frozen boundary
     F90_SYMBOLS = ("caar_launch_f90", "caar_launch_steps_f90")
-    SYMBOLS = BOUNDARY_SYMBOLS + TUNING_SYMBOLS + F90_SYMBOLS
+    # include/caar_dss.h: direct stiffness summation of the new time level — additive, not part of the frozen boundary
+    DSS_SYMBOLS = ("caar_dss_plan_create", "caar_dss_plan_destroy", "caar_dss_plan_info", "caar_dss_launch")
+    SYMBOLS = BOUNDARY_SYMBOLS + TUNING_SYMBOLS + F90_SYMBOLS + DSS_SYMBOLS
 
     def __init__(self, path=LIB_PATH):
         if not os.path.exists(path):
@@ -216,6 +218,12 @@ class CaarLibrary:
         L.caar_set_fused_steps.argtypes = [C.c_int]
         L.caar_has_fused_steps.argtypes = [C.c_int, C.c_int, C.c_int]
         L.caar_map_host.argtypes = [C.POINTER(vp), C.POINTER(_CaarDims), C.POINTER(_CaarArrays), C.c_int]
+        L.caar_dss_plan_create.argtypes = [C.POINTER(vp), C.POINTER(_CaarDims), vp, C.c_int, C.c_int]
+        L.caar_dss_plan_destroy.argtypes = [vp]
+        L.caar_dss_plan_destroy.restype = None
+        L.caar_dss_plan_info.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                         C.POINTER(C.c_int)]
+        L.caar_dss_launch.argtypes = [vp, C.POINTER(_CaarDims), C.c_int, C.POINTER(_CaarArrays), C.c_int, vp, vp]
         L.caar_run_mapped.argtypes = [vp, C.POINTER(_CaarParams)]
         L.caar_unmap_host.argtypes = [vp]
 
@@ -772,3 +780,102 @@ def print_results_2norm(data):
     print("   ---> Norms:\n          ||v||_2  = %.17g\n          ||T||_2  = %.17g\n"
           "          ||dp||_2 = %.17g" % (v, t, d))
     return v, t, d
+
+
+# ----------------------------------------------------------------------------- direct stiffness summation
+DSS_LAYOUTS = {"cxx": 0, "f90": 1}   # CAAR_DSS_LAYOUT_CXX / _F90 (include/caar_dss.h)
+
+
+_DSS_DEFERRED = []   # plan handles closed during a graph capture (a device synchronisation would invalidate it)
+
+
+def _free_deferred_plans(lib):
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        return
+    while _DSS_DEFERRED:
+        lib.lib.caar_dss_plan_destroy(_DSS_DEFERRED.pop())
+
+
+class DssPlan:
+    """The sharer lists of a mesh on one device and the edge buffer of its DSS (caar_dss_plan_create).  `gdof` holds the
+    global id of every GLL point, [ne][np][np] in logical (C++) index order (tinman_sandbox_amd.mesh makes such arrays; a
+    Fortran host's gdofP(np,np,ne) is the same array transposed); `layout` ("cxx" or "f90") is the order of the state
+    arrays and of rspheremp the plan is launched on.  `device`: a torch device or index; None = the current device,
+    "host" = a plan without device storage (info() only).  One DSS may be in flight per plan: it owns the edge buffer."""
+
+    def __init__(self, gdof, nlev, layout="cxx", device=None):
+        self.lib = library()
+        _free_deferred_plans(self.lib)
+        g = np.asarray(gdof)
+        if g.ndim != 3 or g.shape[1] != g.shape[2]:
+            raise CaarError("gdof must be [ne][np][np]")
+        if layout not in DSS_LAYOUTS:
+            raise CaarError("layout must be 'cxx' or 'f90'")
+        self.num_elems, self.np, self.nlev, self.layout = g.shape[0], g.shape[1], int(nlev), layout
+        if device == "host":
+            self.device, idx = None, -1
+        else:
+            self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+            idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
+            self.device = torch.device("cuda", idx)
+        # the C entry point takes the array in the layout's memory order: gdofP(a,b,ie) is [ie][b][a] in C order
+        mem = np.ascontiguousarray((g if layout == "cxx" else g.transpose(0, 2, 1)).astype(np.int64))
+        self.handle = C.c_void_p()
+        dims = _CaarDims(self.np, self.nlev, 1, 1, self.num_elems)
+        self.lib.check(self.lib.lib.caar_dss_plan_create(C.byref(self.handle), C.byref(dims), mem.ctypes.data_as(C.c_void_p),
+                                                         DSS_LAYOUTS[layout], idx), "caar_dss_plan_create")
+
+    def info(self):
+        """dict(unique_points, shared_points, open_points, max_sharers) of caar_dss_plan_info."""
+        u, s, o, m = C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_int()
+        self.lib.check(self.lib.lib.caar_dss_plan_info(self.handle, C.byref(u), C.byref(s), C.byref(o), C.byref(m)),
+                       "caar_dss_plan_info")
+        return {"unique_points": u.value, "shared_points": s.value, "open_points": o.value, "max_sharers": m.value}
+
+    def close(self):
+        """Frees the plan (caar_dss_plan_destroy synchronises the plan's device).  While a graph capture is open on this
+        thread the handle is only set aside, and freed by the next close() or DssPlan() outside a capture."""
+        if getattr(self, "handle", None):
+            _DSS_DEFERRED.append(self.handle)
+            self.handle = None
+        _free_deferred_plans(self.lib)
+
+    def __del__(self):
+        self.close()
+
+    def launch(self, dims, ptrs, tl, rspheremp, stream=None, layout=None, device=None):
+        """caar_dss_launch on raw CaarDims / CaarArrays (the callers below build them); `device`: where the arrays live."""
+        if not self.handle:
+            raise CaarError("the DSS plan is closed")
+        if rspheremp.dtype != torch.float64 or not rspheremp.is_contiguous() or not rspheremp.is_cuda:
+            raise CaarError("rspheremp must be a contiguous float64 device tensor (no CPU fallback)")
+        if rspheremp.numel() != self.num_elems * self.np * self.np:
+            raise CaarError("rspheremp must hold num_elems * np * np values")
+        def index(d):
+            d = torch.device(d)
+            return d.index if d.index is not None else torch.cuda.current_device()
+
+        if self.device is not None and (index(rspheremp.device) != self.device.index or
+                                        (device is not None and index(device) != self.device.index)):
+            raise CaarError("the arrays and rspheremp must live on the plan's device %s (got %s, %s)" % (
+                self.device, device, rspheremp.device))
+        if stream is None:
+            stream = torch.cuda.current_stream(rspheremp.device)
+        with torch.cuda.device(rspheremp.device):
+            rc = self.lib.lib.caar_dss_launch(self.handle, C.byref(dims), DSS_LAYOUTS[layout or self.layout], C.byref(ptrs),
+                                              int(tl), C.c_void_p(rspheremp.data_ptr()), C.c_void_p(stream.cuda_stream))
+        self.lib.check(rc, "caar_dss_launch")
+
+
+def dss(data, plan, rspheremp, tl=None, stream=None):
+    """Direct stiffness summation of T, v and dp3d at time level `tl` (default: control.np1 of a TestData) of C++-layout
+    device arrays, in place (include/caar_dss.h): every GLL point shared by several elements becomes rspheremp * (the sum
+    of its copies, in the contract's order).  `data`: a TestData or an ElementArrays; `rspheremp` a device tensor
+    [ie][np][np]; `plan` a DssPlan with layout "cxx".  Asynchronous on `stream` (default: torch's current stream)."""
+    arrays = data.arrays if isinstance(data, TestData) else data
+    _require_gpu(arrays)
+    if tl is None:
+        if not isinstance(data, TestData):
+            raise CaarError("dss on an ElementArrays needs tl")
+        tl = data.control.np1
+    plan.launch(arrays.dims(), arrays.pointers(), tl, rspheremp, stream, layout="cxx", device=arrays.device)

@@ -159,3 +159,14 @@ def compute_and_apply_rhs_steps(f90, data_or_params, nsteps, rotate=True, stream
     if rotate and not isinstance(data_or_params, tuple):
         for _ in range(nsteps):
             data_or_params.update_time_levels()
+
+
+def dss(f90, plan, rspheremp, tl, stream=None):
+    """Direct stiffness summation of T, v and dp3d at time level `tl` of Fortran-ordered device arrays, in place
+    (include/caar_dss.h, caar.dss): `rspheremp` a device tensor holding rspheremp(np,np,ne) (C-order shape (ne, np, np),
+    the last axis the first Fortran index), `plan` a caar.DssPlan with layout "f90".  `tl` may be a TestData: its
+    control.np1."""
+    _c._require_gpu(f90)
+    if isinstance(tl, _c.TestData):
+        tl = tl.control.np1
+    plan.launch(f90.dims(), f90.pointers(), tl, rspheremp, stream, layout="f90", device=f90.device)
