@@ -75,6 +75,31 @@ def hashed_arrays(np_, nlev, ne, seed, qsize_d=1, timelevels=3):
     return {k: np.ascontiguousarray(v) for k, v in a.items()}
 
 
+def decimal_scales(shape, seed, lo=-3, hi=1):
+    """10**k with integer k in [lo, hi], one per entry of `shape`, from the splitmix hash (the same on every platform)."""
+    n = int(np.prod(shape))
+    k = (splitmix64(np.arange(n, dtype=np.uint64), seed) % np.uint64(hi - lo + 1)).astype(np.int64) + lo
+    return (10.0 ** k.astype(np.float64)).reshape(shape)
+
+
+def stratified_arrays(np_, nlev, ne, seed, qsize_d=1, timelevels=3):
+    """hashed_arrays with slabs of very different sizes: dp3d times the per-level profile geomspace(2, 2000, nlev)/1000 (top
+    levels ~1-3 Pa thick, bottom ones ~3000 Pa), v times 10**k per (element, time level, level) and vn0, omega_p times 10**k
+    per (element, level), k in [-3, 1].  An error confined to a thin level or a weak wind is then large next to its own slab
+    while it stays small next to the field's largest value."""
+    a = hashed_arrays(np_, nlev, ne, seed, qsize_d, timelevels)
+    s = seed * 100 + 50
+    prof = np.geomspace(2.0, 2000.0, nlev) / 1000.0
+    a["elem_state_dp3d"] = a["elem_state_dp3d"] * prof[None, None, :, None, None]
+    a["elem_state_v"] = a["elem_state_v"] * decimal_scales((ne, timelevels, nlev), s + 1)[..., None, None, None]
+    a["elem_derived_vn0"] = a["elem_derived_vn0"] * decimal_scales((ne, nlev), s + 2)[..., None, None, None]
+    a["elem_derived_omega_p"] = a["elem_derived_omega_p"] * decimal_scales((ne, nlev), s + 3)[..., None, None]
+    return {k: np.ascontiguousarray(v) for k, v in a.items()}
+
+
+FAMILIES = {"hashed": hashed_arrays, "stratified": stratified_arrays}
+
+
 def dvv_for(np_, kind="double"):
     O = po.Oracle()
     if np_ == 4 and kind == "double":
@@ -219,6 +244,71 @@ def reference_aliased(R, levels):
     b = copy_arrays(arrs)
     R.compute_and_apply_rhs(b, Dvv, sc)
     return {aliased_key(levels) + "/" + n: b[n] for n in po.ARRAY_NAMES}
+
+
+# ---- compute_and_apply_rhs against an 80-bit truth, slab by slab (tests/test_caar_truth_gpu.py; the conditioning of these
+#      inputs: tests/test_caar_truth.py).  A flavour: (input family, rsplit, qn0, amplified (rrearth 1e-2), (n0, np1, nm1),
+#      element range (nets, nete) of a 3-element case).
+TRUTH_FLAVOURS = (
+    ("hashed", 1, 0, False, (2, 0, 1), (0, None)),
+    ("stratified", 1, -1, True, (1, 2, 0), (0, None)),
+    ("hashed", 0, -1, True, (0, 1, 2), (0, None)),
+    ("stratified", 0, 1, False, (2, 1, 0), (1, 3)),
+    ("stratified", 0, 0, True, (0, 1, 2), (0, None)),
+)
+TRUTH_DEFAULT_SHAPES = ((4, 72), (4, 128), (8, 72))      # every variant of the default kernels
+TRUTH_ANY_NLEV = (2, 3, 5, 17, 26, 47, 50, 64, 65, 79, 85, 96, 97, 100, 127, 129, 200, 256)   # the run-time-level-count kernel
+TRUTH_SPECIALISED_NLEV = (26, 30, 32, 60, 64, 80, 96)    # the extra build's own kernels
+TRUTH_NP4_NLEV = tuple(sorted(set(TRUTH_ANY_NLEV + TRUTH_SPECIALISED_NLEV)))
+TRUTH_NE = 3
+# one case per default kernel over more than 1 000 elements: (np, nlev, ne, nets, nete)
+TRUTH_WIDE = ((4, 72, 1100, 37, 1061), (4, 128, 1100, 37, 1061), (8, 72, 1100, 37, 1061))
+TRUTH_WIDE_FLAVOUR = ("stratified", 1, 0, True, (2, 0, 1), None)
+
+
+def truth_case(np_, nlev, flavour, ne=TRUTH_NE, nets=None, nete=None):
+    """-> (arrays, Dvv, scalars) of one flavour; the seed follows from (np, nlev, flavour)."""
+    family, rsplit, qn0, amplified, (n0, np1, nm1), rng = flavour
+    seed = 1000 + 10 * nlev + np_ + (3000 * (1 + TRUTH_FLAVOURS.index(flavour)) if flavour in TRUTH_FLAVOURS else 0)
+    arrs = FAMILIES[family](np_, nlev, ne, seed)
+    sc = po.default_scalars(nlev)
+    sc.update(n0=n0, np1=np1, nm1=nm1, qn0=qn0, dt2=0.25, eta_ave_w=0.5, rsplit=rsplit,
+              hybi=(np.arange(nlev + 1) / nlev) ** 2)
+    if rng is not None:
+        sc["nets"], sc["nete"] = rng
+    if nets is not None:
+        sc["nets"], sc["nete"] = nets, nete
+    if amplified:
+        sc["rrearth"] = 1e-2
+    return arrs, dvv_for(np_), sc
+
+
+def truth_flavour_name(flavour):
+    family, rsplit, qn0, amplified, (n0, np1, nm1), rng = flavour
+    return "%s_r%d_%s%s_%d%d%d%s" % (family, rsplit, "dry" if qn0 < 0 else "moist", "_amp" if amplified else "", n0, np1, nm1,
+                                     "" if rng is None or rng == (0, None) else "_e%d-%d" % rng)
+
+
+def output_slabs(name, x, sc):
+    """Output `name` of a full array set as [slab][point]: one element at one level (interface for eta_dot_dpdn) of the
+    state at np1 or of a derived array, over the elements [nets, nete)."""
+    if name.startswith("elem_state_"):
+        x = x[:, sc["np1"]]
+    x = x[sc["nets"]:(x.shape[0] if sc.get("nete") is None else sc["nete"])]
+    return x.reshape(x.shape[0] * x.shape[1], -1)
+
+
+def slab_errors(got, truth, sc):
+    """name -> the relative error of every slab, max|got - truth| / max|truth| over that slab alone (in longdouble), for
+    each output; inf where a slab whose truth is all zero is not zero."""
+    out = {}
+    for n in OUTPUT_NAMES:
+        t = output_slabs(n, truth[n], sc)
+        d = np.abs(np.asarray(output_slabs(n, got[n], sc), dtype=np.longdouble) - t).max(axis=1)
+        s = np.abs(t).max(axis=1)
+        e = np.where(d == 0, 0.0, np.where(s > 0, d / np.where(s > 0, s, 1), np.inf))
+        out[n] = e.astype(np.float64)
+    return out
 
 
 def reference_results():

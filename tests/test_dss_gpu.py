@@ -26,7 +26,9 @@ MESHES = {"sphere1": lambda np_: mesh.cubed_sphere_gdof(1, np_), "sphere2": lamb
           "sphere3": lambda np_: mesh.cubed_sphere_gdof(3, np_), "plane1x1": lambda np_: mesh.periodic_plane_gdof(1, 1, np_),
           "plane1x3": lambda np_: mesh.periodic_plane_gdof(1, 3, np_),
           "plane5x4": lambda np_: mesh.periodic_plane_gdof(5, 4, np_)}
-SHAPES = ((4, 72), (4, 128), (4, 17), (4, 2), (8, 72))
+# NP=4 85 levels fill the 32 KiB LDS image exactly (12 x (4*85 + 1) x 8 B); 87, 129 and 200 end on a shorter pass
+# (44 + 43, 65 + 64, 67 + 67 + 66 levels): an overrun past nlev there would land in the next time level
+SHAPES = ((4, 72), (4, 128), (4, 17), (4, 2), (8, 72), (4, 85), (4, 87), (4, 129), (4, 200))
 
 
 def _sparse(gdof):

@@ -510,8 +510,10 @@ __device__ __forceinline__ void caar_np4_element(const KernelArgs& k, Np4Lds<NLE
         p[r] = (k.p_top + (base_dp + ex_dp[r])) + 0.5 * dp[r];  // P:84,94-96 in closed form
         suml[r] = base_div + ex_div[r];                          // P:327,339: sum of divdp above
         rp[r] = recip(p[r]);
-        double ht = (k.Rgas * Tv[r]) * (dp[r] * rp[r]);          // Rgas*T_v*hkl, hkl = dp/p (P:300-302)
-        if (RAGGED && !live_row(r)) ht = 0.0;
+        // Rgas*T_v*hkl, hkl = dp/p (P:300-302).  Dead rows: Tv == 0 and dp == 0 below a positive p, so ht == +0 without a
+        // select — one would keep the compiler from contracting the product into the scan's first add, which it does in
+        // the kernels without dead rows: the two would round the geopotential differently.
+        const double ht = (k.Rgas * Tv[r]) * (dp[r] * rp[r]);
         double in_ht;
         scan_up<SCAN_DPP>(ht, lane, sub, in_ht, ex_ht[r]);
         if (sub == 0) s_tot_ht[t * PP + pt] = in_ht;
@@ -646,9 +648,10 @@ __device__ __forceinline__ void caar_np4_element(const KernelArgs& k, Np4Lds<NLE
         const double facp = half_rdp * eta_hi, facm = half_rdp * eta_lo;   // CaarFunctor.hpp:526-527
         const int ci = PP + t * 64 + ulane;
         // CaarFunctor.hpp:513-546 (the zero rows of s_col stand in for the missing one-sided terms)
-        const double T_vadv = facp * (s_col[0][ci + PP] - T_r) + facm * (T_r - s_col[0][ci - PP]);
-        const double u_vadv = facp * (s_col[1][ci + PP] - u_r) + facm * (u_r - s_col[1][ci - PP]);
-        const double v_vadv = facp * (s_col[2][ci + PP] - v_r) + facm * (v_r - s_col[2][ci - PP]);
+        // (dot2: which product the compiler would contract is otherwise its choice, and differs between launch shapes)
+        const double T_vadv = dot2(facp, s_col[0][ci + PP] - T_r, facm, T_r - s_col[0][ci - PP]);
+        const double u_vadv = dot2(facp, s_col[1][ci + PP] - u_r, facm, u_r - s_col[1][ci - PP]);
+        const double v_vadv = dot2(facp, s_col[2][ci + PP] - v_r, facm, v_r - s_col[2][ci - PP]);
         vtens1 = -u_vadv + v_r * (fcor + vort) - gE0 - glnps1;     // X:326-328
         vtens2 = -v_vadv - u_r * (fcor + vort) - gE1 - glnps2;     // X:332-334
         ttens = -T_vadv - vgrad_T + k.kappa * Tv_r * om;           // X:338
