@@ -264,12 +264,25 @@ TRUTH_NE = 3
 # one case per default kernel over more than 1 000 elements: (np, nlev, ne, nets, nete)
 TRUTH_WIDE = ((4, 72, 1100, 37, 1061), (4, 128, 1100, 37, 1061), (8, 72, 1100, 37, 1061))
 TRUTH_WIDE_FLAVOUR = ("stratified", 1, 0, True, (2, 0, 1), None)
+# the Fortran-order kernels (tests/test_f90_truth_gpu.py): caar_launch_f90 refuses rsplit == 0, so the two Lagrangian flavours
+# above and two more: every kernel meets moist and dry, both Qdp slots, both families, four orders of the time levels, a range
+# that starts and one that ends inside the array
+TRUTH_F90_FLAVOURS = (
+    TRUTH_FLAVOURS[0],
+    TRUTH_FLAVOURS[1],
+    ("stratified", 1, 1, False, (0, 1, 2), (1, 3)),
+    ("hashed", 1, -1, True, (0, 2, 1), (0, 2)),
+)
+# ... and over more than 1 000 elements: the three specialised kernels and one run-time shape per PARK setting
+TRUTH_F90_WIDE = TRUTH_WIDE + ((4, 50, 1100, 37, 1061), (4, 100, 1100, 37, 1061))
+# the flavours with a seed of their own (truth_case), in the order that fixes it: appended to, never reordered
+TRUTH_SEEDED_FLAVOURS = TRUTH_FLAVOURS + tuple(f for f in TRUTH_F90_FLAVOURS if f not in TRUTH_FLAVOURS)
 
 
 def truth_case(np_, nlev, flavour, ne=TRUTH_NE, nets=None, nete=None):
     """-> (arrays, Dvv, scalars) of one flavour; the seed follows from (np, nlev, flavour)."""
     family, rsplit, qn0, amplified, (n0, np1, nm1), rng = flavour
-    seed = 1000 + 10 * nlev + np_ + (3000 * (1 + TRUTH_FLAVOURS.index(flavour)) if flavour in TRUTH_FLAVOURS else 0)
+    seed = 1000 + 10 * nlev + np_ + (3000 * (1 + TRUTH_SEEDED_FLAVOURS.index(flavour)) if flavour in TRUTH_SEEDED_FLAVOURS else 0)
     arrs = FAMILIES[family](np_, nlev, ne, seed)
     sc = po.default_scalars(nlev)
     sc.update(n0=n0, np1=np1, nm1=nm1, qn0=qn0, dt2=0.25, eta_ave_w=0.5, rsplit=rsplit,

@@ -1,4 +1,4 @@
-"""The conditioning of the inputs of tests/test_caar_truth_gpu.py (no GPU): for every flavour and shape it runs, the C oracle
+"""The conditioning of the inputs of tests/test_caar_truth_gpu.py and tests/test_f90_truth_gpu.py (no GPU): for every flavour and shape it runs, the C oracle
 (fp64, bit-identical to the reference C++) is within 1e-13 of the 80-bit truth (oracle/np_oracle.py in numpy.longdouble) in
 every slab of every output, 10x below that file's criterion (a).  A condition on the inputs, not a measurement of the
 kernels: a family whose reference error were close to 1e-12 could not tell a wrong kernel from a right one."""
@@ -23,14 +23,14 @@ def _worst_reference_error(oracle, np_, nlev, flavour, **kw):
 SHAPES = list(cases.TRUTH_DEFAULT_SHAPES) + [(4, nlev) for nlev in cases.TRUTH_NP4_NLEV]
 
 
-@pytest.mark.parametrize("flavour", cases.TRUTH_FLAVOURS, ids=cases.truth_flavour_name)
+@pytest.mark.parametrize("flavour", cases.TRUTH_SEEDED_FLAVOURS, ids=cases.truth_flavour_name)
 @pytest.mark.parametrize("np_,nlev", SHAPES)
 def test_reference_error_of_the_truth_inputs_is_small(oracle, np_, nlev, flavour):
     name, e = _worst_reference_error(oracle, np_, nlev, flavour)
     assert e.max() <= BOUND, (name, int(np.argmax(e)), float(e.max()))
 
 
-@pytest.mark.parametrize("np_,nlev,ne,nets,nete", cases.TRUTH_WIDE)
+@pytest.mark.parametrize("np_,nlev,ne,nets,nete", cases.TRUTH_F90_WIDE)
 def test_reference_error_of_the_wide_truth_inputs_is_small(oracle, np_, nlev, ne, nets, nete):
     name, e = _worst_reference_error(oracle, np_, nlev, cases.TRUTH_WIDE_FLAVOUR, ne=ne, nets=nets, nete=nete)
     assert e.max() <= BOUND, (name, int(np.argmax(e)), float(e.max()))

@@ -198,36 +198,86 @@ def _oracle_steps(oracle, arrs, Dvv, sc, gdof, rsph, nsteps):
     return want
 
 
+STEP_CASES = ((4, 3, 1e-11), (41, 1, 1e-12))   # (ne, steps, tolerance against the oracle's trajectory)
+
+
+def _step_case(oracle, ne, nsteps):
+    g = mesh.cubed_sphere_gdof(ne, 4)
+    arrs = cases.hashed_arrays(4, 72, g.shape[0], seed=ne)
+    Dvv, sc = cases.dvv_for(4), oracle_scalars()
+    rsph = mesh.inverse_mass(g, arrs["elem_spheremp"])
+    return g, arrs, Dvv, sc, rsph, _oracle_steps(oracle, arrs, Dvv, sc, g, rsph, nsteps)
+
+
+def _run_steps(nsteps, step):
+    """`step()` nsteps times: captured in one graph and replayed once if there are several, directly otherwise."""
+    if nsteps > 1:
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            for _ in range(nsteps):
+                step()
+        graph.replay()
+    else:
+        step()
+    torch.cuda.synchronize()
+
+
+def _cxx_steps(g, arrs, Dvv, sc, rsph, nsteps):
+    data = tsa.TestData.from_numpy(arrs, Dvv, sc, device="cuda")
+    data.dvv_device()
+    r = torch.from_numpy(rsph).cuda()
+    plan = tsa.DssPlan(g, 72)
+
+    def step():
+        tsa.compute_and_apply_rhs(data)
+        tsa.dss(data, plan, r)
+        data.update_time_levels()
+
+    _run_steps(nsteps, step)
+    got = data.arrays.to_numpy()
+    plan.close()
+    return got
+
+
 def test_captured_steps_match_the_oracle(oracle):
     """Three steps of caar_launch + DSS with rotating time levels, captured in one graph (ne=4), then one step on every
     element at ne=41."""
-    for ne, nsteps, tol in ((4, 3, 1e-11), (41, 1, 1e-12)):
-        g = mesh.cubed_sphere_gdof(ne, 4)
+    for ne, nsteps, tol in STEP_CASES:
+        g, arrs, Dvv, sc, rsph, want = _step_case(oracle, ne, nsteps)
+        got = _cxx_steps(g, arrs, Dvv, sc, rsph, nsteps)
+        for n in cases.OUTPUT_NAMES:
+            assert cases.scaled_err(got[n], want[n]) <= tol, (ne, n, cases.scaled_err(got[n], want[n]))
+
+
+def test_captured_steps_in_fortran_order_match_the_oracle_and_the_cxx_layout(oracle):
+    """What a Fortran host loops over: caar_launch_f90 + the Fortran-order DSS (plan layout "f90", rspheremp(np,np,ne)) with
+    rotating time levels — three steps captured in one graph at ne=4 and one step on every element at ne=41, against the
+    oracle's trajectory with the tolerances above and, every array, bit for bit against the C++-layout sequence of the same
+    steps (each half is bit-identical across the layouts, so the sequence must be)."""
+    for ne, nsteps, tol in STEP_CASES:
+        g, arrs, Dvv, sc, rsph, want = _step_case(oracle, ne, nsteps)
         E = g.shape[0]
-        arrs = cases.hashed_arrays(4, 72, E, seed=ne)
-        Dvv, sc = cases.dvv_for(4), oracle_scalars()
-        rsph = mesh.inverse_mass(g, arrs["elem_spheremp"])
-        want = _oracle_steps(oracle, arrs, Dvv, sc, g, rsph, nsteps)
-        data = tsa.TestData.from_numpy(arrs, Dvv, sc, device="cuda")
-        data.dvv_device()
-        r = torch.from_numpy(rsph).cuda()
-        plan = tsa.DssPlan(g, 72)
-        if nsteps > 1:
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                for _ in range(nsteps):
-                    tsa.compute_and_apply_rhs(data)
-                    tsa.dss(data, plan, r)
-                    data.update_time_levels()
-            graph.replay()
-        else:
-            tsa.compute_and_apply_rhs(data)
-            tsa.dss(data, plan, r)
-        torch.cuda.synchronize()
-        got = data.arrays.to_numpy()
+        f90 = fl.F90Arrays.from_numpy(fl.to_f90_numpy(arrs), 4, 72, E, device="cuda")
+        scal = tsa.TestData.from_numpy({k: v[:1] for k, v in arrs.items()}, Dvv, sc, device="cuda")   # the scalars only
+        scal.control.nete = E
+        scal.dvv_device()
+        r = torch.from_numpy(np.ascontiguousarray(rsph.transpose(0, 2, 1))).cuda()
+        plan = tsa.DssPlan(g, 72, "f90")
+
+        def step():
+            fl.compute_and_apply_rhs(f90, scal)
+            fl.dss(f90, plan, r, scal)
+            scal.update_time_levels()
+
+        _run_steps(nsteps, step)
+        got = fl.from_f90_numpy(f90.to_numpy())
         plan.close()
         for n in cases.OUTPUT_NAMES:
             assert cases.scaled_err(got[n], want[n]) <= tol, (ne, n, cases.scaled_err(got[n], want[n]))
+        cxx = _cxx_steps(g, arrs, Dvv, sc, rsph, nsteps)
+        for n in tsa.ARRAY_NAMES:
+            a, b = got[n].view(np.int64), cxx[n].view(np.int64)
+            assert np.array_equal(a, b), (ne, n, int((a != b).sum()), np.argwhere(a != b)[:3].tolist())
 
 
 def oracle_scalars():
